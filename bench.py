@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — NMPC solves/sec (batched swarms) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline, solve statistics and the roofline of the
+timed launches).  Everything else it can measure (the result gather of N > 1, the warm closed loop, host buffers, two streams, the
+north-star sweep, LIDAR, the CPU baseline and the CasADi probe) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, the arrays the last step returned (nmpc_solve_batch: x, f, status, iters, kkt; rank 0's
+instances) are written as DIR/<name>.npy in float64.  The inputs are seeded, so two builds can be compared output for output.
 
 With N > 1 and no launcher environment (WORLD_SIZE unset) this process starts N ranks itself, as a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`, before it
@@ -11,7 +18,7 @@ A "step" is one nmpc_solve_batch over one batch of synthetic swarm instances (co
 result write-back to HBM included).  Workload at every N: BASELINE.json configs[2] — 6 robots, horizon N=20, 15 pair rows per
 stage, batch 4096 per GPU (weak scaling: instances are independent, each rank solves its own 4096; no data-path collective).
 The one collective the path has, the result gather (RCCL all_gather of w_out / status / iters), is timed
-separately after the solve steps and reported under "gather".
+separately after the solve steps and reported under "gather" (--full).
 
 --scaling strong [--batch-total T]: ONE global batch of T instances (default: the batch BASELINE.json quotes for the workload — 4096
 for six / ten robots, 8192 for the composite) is split into contiguous shards (nmpc_amd.shard_range), one per rank: what BASELINE
@@ -20,6 +27,7 @@ configs[3] / [4] describe (4096 over 8 GPUs = 512 per GPU, 8192 over 8 = 1024 pe
 Prints ONE JSON line on rank 0 including
   roofline     — the solve kernel against the fp64 vector peak (the kernel issues no MFMA), algorithmic flops of
                  SURVEY.md §8(d): iters * (F_kkt + F_asm) per solve, duration from HIP events on the launch stream;
+and with --full
   cpu_baseline — the C oracle (oracle/nmpc_oracle.c, OpenMP, one instance per thread) timed on this box's host cores on a
                  bounded sample of the same workload ("port");
   sweep        — (N = 1 only) the other north-star shapes, each with its own roofline: m=2 (B=4096 and BASELINE configs[1]'s own 1024) and
@@ -264,6 +272,24 @@ def roofline_block(cfg, B, sum_iters, kern_ms, lib_version, kernel_id, wname="si
     return rl
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(r, out_dir):
+    """--dump-outputs: the arrays of one nmpc_solve_batch result as out_dir/<name>.npy, float64 (status and iters are small integers,
+    exact in float64).  Should they exceed 64 MB in all, every array keeps the same fixed, seeded sample of instances, listed in rows.npy."""
+    arrs = {k: r[k].cpu().numpy().astype(np.float64) for k in ("x", "f", "status", "iters", "kkt")}
+    B = arrs["x"].shape[0]
+    row_bytes = sum(a.nbytes for a in arrs.values()) // B
+    if row_bytes * B > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(SEED0).choice(B, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -272,14 +298,19 @@ def main():
     ap.add_argument("--workload", default="six", choices=["two", "six", "ten", "ten20", "composite"])
     ap.add_argument("--batch", type=int, default=0, help="instances per GPU (default: the workload's)")
     ap.add_argument("--max-iter", type=int, default=2000)
-    ap.add_argument("--closed-loop", type=int, default=20, help="warm closed-loop steps reported as an extra (0 = skip)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="instances for the CPU baseline (0 = skip)")
-    ap.add_argument("--sweep", type=int, default=-1, help="north-star sweep entries (default: on for --gpus 1, 0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run every extra: result gather (N > 1), closed loop, host buffers, two streams, "
+                    "sweep, LIDAR, CPU baseline, CasADi probe (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results to DIR/<name>.npy (float64)")
+    ap.add_argument("--closed-loop", type=int, default=20, help="--full: warm closed-loop steps reported as an extra (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: instances for the CPU baseline (0 = skip)")
+    ap.add_argument("--sweep", type=int, default=-1, help="--full: north-star sweep entries (default: on for --gpus 1, 0 = skip)")
     ap.add_argument("--streams", type=int, default=1, help="launches in flight per GPU: the K timed steps alternate over this many handles, each on its own HIP stream "
                     "(default 1: one launch at a time, as every round has reported `value`; 2 fills the SIMDs a launch's tail leaves idle)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak: every rank its own batch (default); strong: one global batch, sharded")
     ap.add_argument("--batch-total", type=int, default=0, help="--scaling strong: instances of the global batch (default: the workload's BASELINE batch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))        # before any GPU call
@@ -328,11 +359,13 @@ def main():
     more = [nmpc_amd.NmpcSolver(cfg, max_batch=B) for _ in range(max(1, args.streams) - 1)]      # --streams S: S handles, S launches in flight (default 1)
     dt, kern_ms, r = timed_solves(solver, dP, dW0, args.steps, args.warmup, barrier, more)
     del more
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, args.dump_outputs)
 
     iters = r["iters"].cpu().numpy(); status = r["status"].cpu().numpy(); kkt = r["kkt"].cpu().numpy()
     # ---- the result gather of SURVEY.md 8(e): all_gather of w_out / status / iters of every rank's shard, timed on its own
     gather_ms = 0.0
-    if world > 1:
+    if world > 1 and args.full:
         Bg = total if total is not None else B * world      # strong: the shards of the global batch (sizes may differ by one)
         torch.cuda.synchronize()
         for rep in range(4):          # first repetition warms the communicator up
@@ -380,16 +413,17 @@ def main():
         "roofline": roofline_block(cfg, B, float(allst[0, 1]), float(allst[0, 5]), lib_version, kernel_id, args.workload),
         "note": ROOFLINE_NOTE,
     }
-    if world > 1:
+    if world > 1 and args.full:
         per_rank_bytes = B * (cfg.n_var * 8 + 8)
         gms = float(allst[:, 6].max())
         out["gather"] = {"collective": "all_gather of w_out [B, n_var] f64 + status + iters (nmpc_amd.gather_results)", "backend": dist.get_backend(),
                          "ms": gms, "bytes_per_rank_shard": per_rank_bytes, "recv_GBps_per_rank": per_rank_bytes * (world - 1) / (gms * 1e-3) / 1e9 if gms > 0 else None,
                          "note": "timed separately from the solve steps (mean of 3 after a warm-up); not part of `value`, which is the device-resident solve"}
+    extras = world == 1 and args.full          # every block below measures something besides `value`: --full only
     # warm closed loop of SURVEY.md 8(d): 20 receding-horizon steps, each = solve + device shift/plant step (a13 + a11);
     # and the same cold solve with HOST buffers at the boundary (H2D of p, w0 and D2H of w included).  Both are extras:
     # `value` above is the device-resident cold solve.
-    if world == 1 and args.closed_loop > 0:
+    if extras and args.closed_loop > 0:
         try:
             nx = cfg.nx
             Pc, Wc = dP.clone(), dW0.clone()
@@ -446,7 +480,7 @@ def main():
     # two launches in flight: the same cold batch solved through TWO handles (two workspaces) on two HIP streams, launches alternating.  A launch of
     # 4096 lasts as long as its longest solve; the second stream's wavefronts run on the SIMDs the first launch's tail leaves idle.  An extra:
     # `value` above stays one launch at a time on one stream.
-    if world == 1 and args.closed_loop > 0:
+    if extras and args.closed_loop > 0:
         try:
             s2 = nmpc_amd.NmpcSolver(cfg, max_batch=B)
             v2, ms2, same = two_stream_rate([solver, s2], dP, dW0, r)
@@ -457,7 +491,7 @@ def main():
             out.setdefault("extras_failed", []).append("closed_loop: %r" % (e_,))
     # north-star sweep: N_robots in {2, 6, 10}, N=20, batch 4096 (+ BASELINE configs[3] and [4]); one warm-up + two timed launches each
     do_sweep = args.sweep if args.sweep >= 0 else (1 if (world == 1 and args.workload == "six" and not args.batch) else 0)
-    if world == 1 and do_sweep:
+    if extras and do_sweep:
         try:
             del solver
             out["sweep"] = []
@@ -484,7 +518,7 @@ def main():
             out.setdefault("extras_failed", []).append("sweep: %r" % (e_,))
     # LIDAR-ray distance-state NMPC (the file BASELINE configs[4] names, AllScripts/obs_avoid_static_first_scenario_v4.py: one robot,
     # 13 states, N=100, Nc=50; SURVEY.md 0 mismatch 2): one wavefront per instance, the instance's workspace lives in HBM/L2
-    if world == 1 and do_sweep:
+    if extras and do_sweep:
         try:
             lc = nmpc_amd.lidar_v4()
             Bl = 4096
@@ -558,7 +592,7 @@ def main():
             out.setdefault("extras_failed", []).append("sweep: %r" % (e_,))
     # (measured last: the OpenMP team of the oracle keeps the host cores spinning for a while after it returns)
     # CPU baseline: the C oracle on this box's host cores, bounded sample of the same workload
-    if world == 1 and args.cpu_sample != 0:
+    if extras and args.cpu_sample != 0:
         try:
             from oracle import oracle_lib as O
             from tests import helpers as Hh
@@ -581,7 +615,7 @@ def main():
             out.setdefault("extras_failed", []).append("cpu: %r" % (e_,))
     # the extra CPU row of BASELINE.md 3 / SURVEY.md 8(d): nlpsol('ipopt') on the identical NLP built through the CasADi API by the build's own
     # generator (oracle/casadi_probe.py) — only if casadi happens to be importable on this box; the record says which
-    if world == 1 and args.cpu_sample != 0:
+    if extras and args.cpu_sample != 0:
         try:
             from oracle import casadi_probe as CP
             from tests import helpers as Hh

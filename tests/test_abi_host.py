@@ -232,6 +232,34 @@ def test_bench_roofline_inputs_match_survey():
         assert (cfg.m, cfg.N, b) == (m, N, B)
 
 
+def test_bench_dump_outputs_writes_float64_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array of the solve result as <name>.npy in float64; above the size limit the same seeded rows of
+    every array, listed in rows.npy, and the same rows on every run."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    B, n = 300, 7
+    rng = np.random.default_rng(1)
+    r = {"x": torch.as_tensor(rng.standard_normal((B, n))), "f": torch.as_tensor(rng.standard_normal(B)), "kkt": torch.as_tensor(rng.random(B)),
+         "status": torch.as_tensor(rng.integers(0, 5, B), dtype=torch.int32), "iters": torch.as_tensor(rng.integers(1, 300, B), dtype=torch.int32)}
+    bench.dump_outputs(r, str(tmp_path / "all"))
+    for k, v in r.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, v.numpy().astype(np.float64)), k
+    assert not (tmp_path / "all" / "rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * (n + 4) * 8 + 800)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(r, str(tmp_path / d))
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 100 and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    idx = rows.astype(np.int64)
+    assert len(set(idx)) == 100 and idx.min() >= 0 and idx.max() < B
+    for k, v in r.items():
+        assert np.array_equal(np.load(tmp_path / "s1" / (k + ".npy")), v.numpy()[idx].astype(np.float64)), k
+    assert sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in os.listdir(tmp_path / "s1")) <= bench.DUMP_LIMIT_BYTES
+
+
 def test_bench_self_launches_ranks_and_never_reports_one_gpu_for_n(built):
     """ADVICE r1 / VERDICT r1: `python bench.py --gpus 2` without a launcher must start 2 ranks itself (before any GPU call) and must
     never print an n_gpus=1 line for it.  Without GPUs the ranks exit non-zero ("needs a GPU") and so does the parent; with

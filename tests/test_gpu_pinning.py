@@ -482,7 +482,7 @@ def test_bench_two_ranks_rehearsal(built, scaling):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NMPC_BENCH_REHEARSAL="1")
     env.pop("NMPC_KERNEL", None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--sweep", "0", "--cpu-sample", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "1", "--sweep", "0", "--cpu-sample", "0",
            "--closed-loop", "0", "--workload", "two", "--scaling", scaling] + (["--batch-total", "300"] if scaling == "strong" else ["--batch", "128"])
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -492,3 +492,36 @@ def test_bench_two_ranks_rehearsal(built, scaling):
     assert d["n_gpus"] == 2 and d["config"]["ranks"] == 2 and d["config"]["backend"] == "gloo" and d["scaling"] == scaling
     assert d["value"] > 0 and d["solve_stats"]["converged_frac"] == 1.0 and d["gather"]["ms"] > 0
     assert d["config"]["batch_total"] == (300 if scaling == "strong" else 256) and d["config"]["batch_per_gpu"] == (150 if scaling == "strong" else 128)
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(built, tmp_path):
+    """bench.py without --full: the timed steps and the result line only (no extra block); --dump-outputs writes the last step's result,
+    and the same seeded inputs give the same outputs in a second run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("NMPC_KERNEL", None)
+    runs = []
+    for k in range(2):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "two", "--batch", "128",
+               "--dump-outputs", str(tmp_path / str(k))]
+        out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "solves/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - 128 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("closed_loop", "host_buffers", "two_streams", "sweep", "cpu_baseline", "casadi", "gather", "extras_failed"):
+        assert k not in d, k
+    import nmpc_amd
+    n_var = nmpc_amd.centralized_two_robots(N=20).n_var
+    got = {n: np.load(tmp_path / "0" / (n + ".npy")) for n in ("x", "f", "status", "iters", "kkt")}
+    assert got["x"].shape == (128, n_var) and all(a.dtype == np.float64 for a in got.values())
+    assert float((got["status"] == 0).mean()) == d["solve_stats"]["converged_frac"] and float(got["iters"].max()) == d["solve_stats"]["max_iters"]
+    for n, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "1" / (n + ".npy"))), n
+

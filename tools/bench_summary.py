@@ -1,4 +1,4 @@
-"""Development aid: one line per workload of a bench.py JSON line.   python tools/bench_summary.py [bench.json]"""
+"""Development aid: one line per workload of a `bench.py --full` JSON line.   python tools/bench_summary.py [bench.json]"""
 import json, sys
 d = json.load(open(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/bench.json"))
 rl = d["roofline"]; ss = d["solve_stats"]

@@ -1,4 +1,4 @@
-"""Development aid: the "Measured" table of DESIGN.md 7 from a bench.py record.   python tools/design_table.py [profiles/current/bench.json]"""
+"""Development aid: the "Measured" table of DESIGN.md 7 from a `bench.py --full` record.   python tools/design_table.py [profiles/current/bench.json]"""
 import json, sys
 d = json.load(open(sys.argv[1] if len(sys.argv) > 1 else "profiles/current/bench.json"))
 rows = []
