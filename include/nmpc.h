@@ -194,6 +194,29 @@ int32_t nmpc_step_batch(nmpc_handle_t *h, int32_t B, double *p, double *w, doubl
                         double *kkt, int32_t *order, void *stream);
 
 /*
+ * Obstacles as per-instance solve parameters, static or moving.  The three calls below are nmpc_solve_batch_ordered, nmpc_step_batch and
+ * nmpc_eval_batch with the obstacle field of every instance instead of the handle's:
+ *   obs [B][S][K][3] fp64 device, (ox, oy, r) per obstacle; K = cfg.n_obs of the handle; S = obs_stages, 1 or N.
+ *   Stage k's obstacle rows (k = 0..N-1, evaluated at X_k) use entry k when S == N and entry 0 when S == 1, i.e. entry k is the obstacle at
+ *   the time of X_k (a moving obstacle: its predicted path; a growing radius: prediction uncertainty).  The handle's cfg.obs values are not
+ *   read by these calls; a handle for K parametric obstacles is a config with n_obs = K.
+ * The row layout, n_g, the bounds (margin on every obstacle row) and the status codes are those of the plain calls; NMPC_STATUS_INFEASIBLE_X0
+ * uses entry 0 of the instance's own field.  The field is read by the instance, never by the workgroup: with a dispatch-order hint, workgroup
+ * g solves instance order[g] with obs[order[g]].  Given the same field as the config, the results are bit-identical to the plain calls.
+ * Returns NMPC_E_ARG when cfg.n_obs == 0, obs == NULL with B > 0, or obs_stages is neither 1 nor N; otherwise the errors of the plain call.
+ * Kernels: only the column-per-lane kernel has the per-instance field, in every shape (throughput; latency, two or four wavefronts per
+ * instance); where the plain call would run the element-per-lane kernel, these run the column kernel's throughput shape.  Handles that run on
+ * kernel 1 or 2 (horizons too long for the column kernel's LDS, or nmpc_options_t.kernel = 1 / 2) get NMPC_E_UNSUPPORTED from the two solve
+ * calls; nmpc_eval_batch_obs works on every handle.
+ */
+int32_t nmpc_solve_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
+                             double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order, void *stream);   /* order may be NULL */
+int32_t nmpc_step_batch_obs(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *obs, int32_t obs_stages, double *obj,
+                            int32_t *status, int32_t *iters, double *kkt, int32_t *order, void *stream);
+int32_t nmpc_eval_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *obs, int32_t obs_stages, double *f, double *g,
+                            void *stream);
+
+/*
  * Odometry front-end of the scripts' callbacks (AS/centralized_two_robots_implementation.py:18-37): for n robots,
  *   odom [n][4] = (x_r, y_r, q_z, q_w) wheel-odometry pose in the robot's own start frame (q_w is carried but, as in the
  *                  reference, not used: yaw = 2 asin(q_z)),

@@ -18,10 +18,11 @@ SOURCES = ["nmpc_kernels.hip", "nmpc_solve_lds.hip", "nmpc_solve_col.hip", "nmpc
 # same pass, measured A/B in one session (round 3): two robots +2.3 %, six +3.7 % (B = 16384: +5.2 %), composite +2.3 %, ten +-0.
 FILE_FLAGS = {"nmpc_lidar.hip": os.environ.get("NMPC_LIDAR_FLAGS", "-mllvm -disable-machine-licm").split(),
               "nmpc_solve_col.hip": os.environ.get("NMPC_COL_FLAGS", "-mllvm -disable-machine-licm").split()}
-# compile units: (source, object name, extra flags).  The column-per-lane kernel is compiled in three parts (team sizes 1..5, 6..8, 9..10:
-# ~120 s each instead of ~350 s in one unit; see NMPC_COL_PART in the source); with NMPC_COL_ONLY_M (development) in one.
+# compile units: (source, object name, extra flags).  The column-per-lane kernel is compiled in six parts (team sizes 1..5, 6..8, 9..10, and the
+# same for the per-instance obstacle field: ~120 s each instead of ~350 s per field source in one unit; see NMPC_COL_PART in the source); with
+# NMPC_COL_ONLY_M (development) in one.
 UNITS = [(s, s.rsplit(".", 1)[0], []) for s in SOURCES if s != "nmpc_solve_col.hip"] \
-    + [("nmpc_solve_col.hip", "nmpc_solve_col_p%d" % k, ["-DNMPC_COL_PART=%d" % k]) for k in (1, 2, 3)]
+    + [("nmpc_solve_col.hip", "nmpc_solve_col_p%d" % k, ["-DNMPC_COL_PART=%d" % k]) for k in (1, 2, 3, 4, 5, 6)]
 DEPS = SOURCES + ["nmpc_device.h", "nmpc_solve_common.h"] + [os.path.join("..", "..", "include", h) for h in ("nmpc.h", "nmpc_lidar.h", "nmpc_constants.h", "nmpc_debug.h")]
 
 

@@ -38,8 +38,13 @@ class EpisodeResult:
 
 def simulate_closed_loop(solver: NmpcSolver, x0, goals, max_steps: int, stop_tol: float = 5e-2, coll_tol: float = 1e-6,
                          window: int = 10, move_tol: float = 1e-3, keep_states: bool = False,
-                         on_failure: str = "apply", order_hint: bool = True) -> EpisodeResult:
+                         on_failure: str = "apply", order_hint: bool = True, obstacle_paths=None) -> EpisodeResult:
     """Run B closed-loop episodes.  x0: [B, n_x]; goals: [B, n_x] or [B, G, n_x] (visited in order).
+
+    obstacle_paths: optional [B, L, K, 3], L >= max_steps + N, K = len(cfg.obstacles): (ox, oy, r) of every obstacle at every control period
+    (moving obstacles, per-swarm worlds).  The solve of period t sees rows t .. t+N-1 (its stage k: the obstacles at the time of X_k, the
+    solver's obstacles= field); the clearance statistic and collision_free check the state of period t against row t.  None: the config's
+    obstacles, static.
 
     on_failure: what a swarm does in a period whose solve did not converge (status != 0; ~1 in 1e5 warm solves stall at an
     infeasible stationary point): "apply" = the reference's behaviour, the returned iterate's first control is applied;
@@ -68,6 +73,14 @@ def simulate_closed_loop(solver: NmpcSolver, x0, goals, max_steps: int, stop_tol
     clear = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
     iu = torch.triu_indices(m, m, 1, device=dev)
     obs = torch.tensor(cfg.obstacles, dtype=torch.float64, device=dev).reshape(-1, 3) if len(cfg.obstacles) else None
+    paths = field = None
+    if obstacle_paths is not None:
+        K = len(cfg.obstacles)
+        paths = torch.as_tensor(obstacle_paths, dtype=torch.float64, device=dev)
+        if K == 0 or paths.dim() != 4 or paths.shape[0] != B or paths.shape[1] < max_steps + cfg.N or paths.shape[2] != K or paths.shape[3] != 3:
+            raise ValueError(f"obstacle_paths must be [B, L, K, 3] with B={B}, L >= max_steps + N = {max_steps + cfg.N}, K = len(cfg.obstacles) = {K} > 0; "
+                             f"got {tuple(paths.shape)}")
+        field = torch.empty((B, cfg.N, K, 3), dtype=torch.float64, device=dev)      # the solve's window of the paths, contiguous
     hist, its, states = [], [], []
     prev_iters = None
     failed = total = 0
@@ -79,17 +92,21 @@ def simulate_closed_loop(solver: NmpcSolver, x0, goals, max_steps: int, stop_tol
     pbuf = torch.empty((B, 2 * nx), dtype=torch.float64, device=dev)
     order = torch.arange(B, dtype=torch.int32, device=dev) if order_hint else None
 
-    def track(xc):
+    def track(xc, t):
         nonlocal mind, clear
         xy = xc.reshape(B, m, 3)[:, :, :2]
         if m > 1:
             d = (xy[:, iu[0]] - xy[:, iu[1]]).norm(dim=2).min(dim=1).values
             mind = torch.minimum(mind, d)
-        if obs is not None:
+        if paths is not None:      # the obstacles of period t, per swarm
+            ot = paths[:, t]
+            c = ((xy[:, :, None, :] - ot[:, None, :, :2]).norm(dim=3) - cfg.rob_dim - ot[:, None, :, 2]).amin(dim=(1, 2))
+            clear = torch.minimum(clear, c)
+        elif obs is not None:
             c = ((xy[:, :, None, :] - obs[None, None, :, :2]).norm(dim=3) - cfg.rob_dim - obs[None, None, :, 2]).amin(dim=(1, 2))
             clear = torch.minimum(clear, c)
 
-    track(x)
+    track(x, 0)
     if keep_states:
         states.append(x.clone())
     steps = 0
@@ -107,13 +124,16 @@ def simulate_closed_loop(solver: NmpcSolver, x0, goals, max_steps: int, stop_tol
         xs = g[ar, gi]
         # dispatch-order hint: the swarms that needed the most iterations in the previous period go first (rank correlation of
         # consecutive periods' iteration counts 0.6-0.7; -12 % launch time on the six-robot batch)
+        if field is not None:
+            field.copy_(paths[:, step:step + cfg.N])
         if fused:
             pbuf[:, :nx] = x; pbuf[:, nx:] = xs
-            r = solver.step_batch(pbuf, w, order)
+            r = solver.step_batch(pbuf, w, order, obstacles=field)
             xn = pbuf[:, :nx].clone()
         else:
             p = torch.cat([x, xs], dim=1)
-            r = solver.solve_batch(p, w, order=None if (prev_iters is None or not order_hint) else torch.argsort(prev_iters, descending=True))
+            r = solver.solve_batch(p, w, order=None if (prev_iters is None or not order_hint) else torch.argsort(prev_iters, descending=True),
+                                   obstacles=field)
             prev_iters = r["iters"]
             plan = torch.where((r["status"] == 0)[:, None], r["x"], w)
             w, xn = solver.shift_batch(p, plan, plant=True)
@@ -122,7 +142,7 @@ def simulate_closed_loop(solver: NmpcSolver, x0, goals, max_steps: int, stop_tol
         its.append(r["iters"].double().mean())
         # a swarm that has arrived keeps solving (its problem is the fixed point) but stays where it is
         x = torch.where(arrived[:, None], x, xn)
-        track(x)
+        track(x, step + 1)
         hist.append(x.clone())
         if len(hist) > window:
             hist.pop(0)
@@ -139,7 +159,7 @@ def simulate_closed_loop(solver: NmpcSolver, x0, goals, max_steps: int, stop_tol
     ok = torch.ones(B, dtype=torch.bool, device=dev)
     if m > 1:
         ok &= mind >= cfg.dmin - coll_tol
-    if obs is not None:
+    if obs is not None or paths is not None:
         ok &= clear >= cfg.margin - coll_tol
     return EpisodeResult(steps=steps, arrived=arrived.cpu().numpy(), arrival_step=arrival.cpu().numpy(), collision_free=ok.cpu().numpy(),
                          min_pair_distance=mind.cpu().numpy(), deadlocked=dead.cpu().numpy(), final_error=err.cpu().numpy(),
@@ -153,11 +173,14 @@ def simulate_closed_loop_fleets(cfg, x0, goals, max_steps: int, fleets: int = 4,
     fleet.  A control period of one fleet lasts as long as its longest solve; the periods of the other fleets run on the SIMDs that tail leaves idle
     (six robots, 4096 swarms: 355 k -> 430-440 k solves/s as four fleets; which streams run concurrently is the runtime's choice).
     Every swarm's episode is what simulate_closed_loop computes for it: swarms are independent, only the dispatch-order hint acts per fleet.
-    cfg: ProblemConfig; the other arguments as in simulate_closed_loop."""
+    cfg: ProblemConfig; the other arguments as in simulate_closed_loop (obstacle_paths [B, L, K, 3] is sliced per fleet, as x0 and goals)."""
     import threading
     from .distributed import shard_range
     x0 = np.asarray(x0.cpu() if hasattr(x0, "cpu") else x0, dtype=np.float64).reshape(-1, cfg.nx)
     goals = np.asarray(goals.cpu() if hasattr(goals, "cpu") else goals, dtype=np.float64)
+    paths = kw.pop("obstacle_paths", None)
+    if paths is not None:
+        paths = np.asarray(paths.cpu() if hasattr(paths, "cpu") else paths, dtype=np.float64)
     B = x0.shape[0]
     fleets = max(1, min(int(fleets), B))
     parts = [shard_range(B, f, fleets) for f in range(fleets)]
@@ -170,7 +193,7 @@ def simulate_closed_loop_fleets(cfg, x0, goals, max_steps: int, fleets: int = 4,
         lo, hi = parts[f]
         try:
             with torch.cuda.device(solvers[f].device), torch.cuda.stream(streams[f]):
-                res[f] = simulate_closed_loop(solvers[f], x0[lo:hi], goals[lo:hi], max_steps, **kw)
+                res[f] = simulate_closed_loop(solvers[f], x0[lo:hi], goals[lo:hi], max_steps, obstacle_paths=None if paths is None else paths[lo:hi], **kw)
         except Exception as e:      # re-raised in the caller's thread
             err[f] = e
     th = [threading.Thread(target=run, args=(f,)) for f in range(fleets)]

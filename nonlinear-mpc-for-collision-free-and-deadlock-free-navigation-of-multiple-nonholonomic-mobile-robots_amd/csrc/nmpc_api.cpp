@@ -211,6 +211,14 @@ static int kernel_for_batch(const nmpc_handle_t *h, int32_t B, bool ordered = fa
     return kern;
 }
 
+// the kernel of an *_obs call (column kernel only, h->kernel == 3): the plain call's choice, with the column kernel's throughput shape where that
+// would be the element-per-lane kernel
+static int kernel_for_batch_obs(const nmpc_handle_t *h, int32_t B, bool ordered = false)
+{
+    const int k = kernel_for_batch(h, B, ordered);
+    return k == 2 ? 3 : k;
+}
+
 // latency shape: two wavefronts per instance (1), or four (2) for five / six robots whose stage-parallel phases have more than 1000 items
 // (obstacle rows: (N-1) m K) while the batch fits twice the instances that shape holds at once (2 per CU)
 static int lat_waves_shape(const nmpc_handle_t *h, int32_t B)
@@ -220,10 +228,21 @@ static int lat_waves_shape(const nmpc_handle_t *h, int32_t B)
     return (h->cfg.m >= 5 && h->cfg.m <= 6 && items > 1000 && B <= 2 * h->lat_slots4) ? 2 : 1;
 }
 
+// the per-instance obstacle field of the *_obs entry points: NMPC_OK, or the error of a bad field (obs may be NULL only for an empty batch)
+static int32_t obs_field_check(const nmpc_handle_t *h, int32_t B, const double *obs, int32_t obs_stages)
+{
+    if (!h) return NMPC_E_ARG;
+    if (h->cfg.n_obs == 0 || (obs_stages != 1 && obs_stages != h->cfg.N) || (B > 0 && !obs)) return NMPC_E_ARG;
+    return NMPC_OK;
+}
+
+// obs != NULL: the obstacle field of the instances, [B][obs_stages][n_obs][3] (checked by obs_field_check), read by the column kernel's
+// per-instance field instantiations; handles that run on kernel 1 or 2 have none
 static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                          int32_t *iters, double *kkt, const int32_t *order, void *stream)
+                          int32_t *iters, double *kkt, const int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    if (obs && h->kernel != 3) return NMPC_E_UNSUPPORTED;      // horizon beyond the column kernel's LDS, or a pin to kernel 1 / 2
     if (B == 0) return NMPC_OK;      /* empty batch: nothing to read or write, pointers may be null */
     if (!p || !w0 || !w_out) return NMPC_E_ARG;
     DeviceScope dev(h->device);
@@ -231,6 +250,11 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
     nmpc::KParams P = h->P;
     P.order = order;
     P.order_bad = h->ord_chk + B;
+    if (obs) {
+        P.ofield.ptr = obs;
+        P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
+        P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
+    }
     if (order && nmpc::launch_order_check(B, order, h->ord_chk, h->ord_chk + B, (hipStream_t)stream) != hipSuccess) return NMPC_E_HIP;
     // Launch shape.  The column-per-lane kernel (one wave per instance, two instances per SIMD up to six robots) is the
     // throughput path.  A batch that cannot fill those slots is a latency problem instead (the launch lasts as long as its longest
@@ -238,7 +262,11 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
     // faster.  Measured (solves/s, column | element), six robots: B=256 14.7 k | 16.7 k, 512 28.6 k | 31.0 k, 1024 54.0 k | 46.4 k,
     // 2048 97 k | 89 k, 4096 164 k | 104 k, 8192 205 k | 131 k, 16384 251 k | 145 k; ten robots N=20: B=256 10.4 k | 11.9 k,
     // 512 13.1 k | 13.4 k, 1024 25.5 k | 23.0 k, 2048 41.5 k | 25.5 k, 4096 59 k | 27 k; N=30: B=256 3.4 k | 3.8 k, 512 5.7 k | 4.7 k.
-    const int kern = kernel_for_batch(h, B, order != nullptr);
+    const int kern = obs ? kernel_for_batch_obs(h, B, order != nullptr) : kernel_for_batch(h, B, order != nullptr);
+    if (obs) {
+        hipError_t e = nmpc::launch_solve_col_obs(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, kern == 4 ? lat_waves_shape(h, B) : 0);
+        return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+    }
     hipError_t e = (kern == 1)   ? nmpc::launch_solve(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, (hipStream_t)stream)
                    : (kern == 2) ? nmpc::launch_solve_lds(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream)
                                  : nmpc::launch_solve_col(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, kern == 4 ? lat_waves_shape(h, B) : 0);
@@ -257,16 +285,17 @@ int32_t nmpc_solve_batch_ordered(nmpc_handle_t *h, int32_t B, const double *p, c
     return solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream);
 }
 
-int32_t nmpc_step_batch(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, double *obj, int32_t *status, int32_t *iters, double *kkt,
-                        int32_t *order, void *stream)
+static int32_t step_impl(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, double *obj, int32_t *status, int32_t *iters, double *kkt,
+                         int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    if (obs && h->kernel != 3) return NMPC_E_UNSUPPORTED;
     if (B == 0) return NMPC_OK;
     if (!p || !w || !w_sol || w == w_sol) return NMPC_E_ARG;
     int32_t *it = iters ? iters : h->it_buf;
     int32_t *stt = status ? status : h->st_buf;
     // 1. the solve, dispatched in the caller's order (checked to be a permutation; ignored otherwise)
-    int32_t rc = solve_impl(h, B, p, w, w_sol, obj, stt, it, kkt, order, stream);
+    int32_t rc = solve_impl(h, B, p, w, w_sol, obj, stt, it, kkt, order, stream, obs, obs_stages);
     if (rc != NMPC_OK) return rc;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
@@ -279,6 +308,32 @@ int32_t nmpc_step_batch(nmpc_handle_t *h, int32_t B, double *p, double *w, doubl
     return NMPC_OK;
 }
 
+int32_t nmpc_step_batch(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, double *obj, int32_t *status, int32_t *iters, double *kkt,
+                        int32_t *order, void *stream)
+{
+    return step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream);
+}
+
+int32_t nmpc_solve_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
+                             double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order, void *stream)
+{
+    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    int32_t rc = obs_field_check(h, B, obs, obs_stages);
+    if (rc != NMPC_OK) return rc;
+    if (B == 0) return h->kernel == 3 ? NMPC_OK : NMPC_E_UNSUPPORTED;
+    return solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages);
+}
+
+int32_t nmpc_step_batch_obs(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *obs, int32_t obs_stages, double *obj,
+                            int32_t *status, int32_t *iters, double *kkt, int32_t *order, void *stream)
+{
+    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    int32_t rc = obs_field_check(h, B, obs, obs_stages);
+    if (rc != NMPC_OK) return rc;
+    if (B == 0) return h->kernel == 3 ? NMPC_OK : NMPC_E_UNSUPPORTED;
+    return step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages);
+}
+
 int32_t nmpc_eval_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *w, double *f, double *g, void *stream)
 {
     if (!h || B < 0) return NMPC_E_ARG;
@@ -287,6 +342,24 @@ int32_t nmpc_eval_batch(nmpc_handle_t *h, int32_t B, const double *p, const doub
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
     hipError_t e = nmpc::launch_eval(h->P, h->cfg.m, B, p, w, f, g, (hipStream_t)stream);
+    return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+int32_t nmpc_eval_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *obs, int32_t obs_stages, double *f, double *g,
+                            void *stream)
+{
+    if (!h || B < 0) return NMPC_E_ARG;
+    int32_t rc = obs_field_check(h, B, obs, obs_stages);
+    if (rc != NMPC_OK) return rc;
+    if (B == 0) return NMPC_OK;
+    if (!p || !w) return NMPC_E_ARG;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    nmpc::KParams P = h->P;
+    P.ofield.ptr = obs;
+    P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
+    P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
+    hipError_t e = nmpc::launch_eval(P, h->cfg.m, B, p, w, f, g, (hipStream_t)stream, true);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 

@@ -17,7 +17,13 @@ struct KParams {
     double T, dmin2, vmax, wmax, xymax, thmax, robdim, margin, pad_value, tol, mu_init;
     double q[3], r[2];
     double rho_el;        // penalty of the elastic phase (NMPC_ELASTIC_RHO)
-    double obs[3 * NMPC_MAX_OBSTACLES];
+    union {      // the obstacle field: one of the two, chosen at compile time by the kernel instantiation (ObsField, nmpc_solve_common.h)
+        double obs[3 * NMPC_MAX_OBSTACLES];      // (ox, oy, obs_r) per obstacle: the handle's config field, the same for every instance and stage
+        struct {
+            const double *ptr;                   // [B][S][K][3] device: per-instance field of the *_obs entry points (S = 1 or N)
+            int32_t istride, sstride;            // doubles per instance (S K 3) and per stage (K 3 when S = N, 0 when S = 1)
+        } ofield;
+    };
     // per-instance workspace carve-up, in doubles
     int64_t stride;
     int32_t trace_inst;   // NMPC_PROFILE builds: instance whose per-iteration trace is recorded
@@ -39,9 +45,11 @@ hipError_t launch_solve_lds(const KParams &P, int m, int B, const double *p, con
 size_t lds_kernel_bytes(const KParams &P, int m);
 hipError_t launch_solve_col(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
                             int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape);      // shape: 0 throughput, 1 latency (two wavefronts per instance)
+hipError_t launch_solve_col_obs(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
+                                int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape);      // launch_solve_col with the obstacle field P.ofield
 size_t col_kernel_bytes(const KParams &P, int m, int shape);
 void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride);
-hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st);
+hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);
 hipError_t launch_odometry(long n, const double *odom, const double *init, double *pose, int wrap, hipStream_t st);

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "nmpc_device.h"
+#include "nmpc_solve_common.h"
 
 namespace nmpc {
 
@@ -876,11 +877,15 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
 }
 
 // ------------------------------------------------------------------------------------------
-// f and g in the reference's row order (C6:278,314,318-331): streaming, one thread per (instance, stage)
-template <int M_>
+// f and g in the reference's row order (C6:278,314,318-331): streaming, one thread per (instance, stage).
+// MS: the team size, plus NMPC_EVAL_OBS for the instantiations of nmpc_eval_batch_obs, which read the per-instance obstacle field (ObsField,
+// nmpc_solve_common.h) — a bit of the template argument, as the column kernel's DL, so that the plain instantiations keep their names and code.
+constexpr int NMPC_EVAL_OBS = 16;
+template <int MS>
 __global__ __launch_bounds__(256) void eval_kernel(const KParams P, int B, const double *__restrict__ p_in, const double *__restrict__ w,
                                                     double *__restrict__ f_out, double *__restrict__ g_out)
 {
+    constexpr int M_ = MS % NMPC_EVAL_OBS, OS = MS / NMPC_EVAL_OBS;
     constexpr int NX = Geo<M_>::NX, NU = Geo<M_>::NU, NP = Geo<M_>::NP;
     const int N = P.N;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -918,10 +923,11 @@ __global__ __launch_bounds__(256) void eval_kernel(const KParams P, int B, const
                 double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1];
                 gk[o++] = dx * dx + dy * dy;
             }
+        const ObsField<OS> OB(P, (size_t)b);
         for (int i = 0; i < M_; i++)
             for (int q = 0; q < P.K; q++) {
-                double dx = x[3 * i] - P.obs[3 * q], dy = x[3 * i + 1] - P.obs[3 * q + 1];
-                gk[o++] = sqrt(dx * dx + dy * dy) - P.robdim - P.obs[3 * q + 2];
+                double dx = x[3 * i] - OB(k, q, 0), dy = x[3 * i + 1] - OB(k, q, 1);
+                gk[o++] = sqrt(dx * dx + dy * dy) - P.robdim - OB(k, q, 2);
             }
     }
     if (f_out) atomicAdd(&f_out[b], fs);   // <= N adds per instance; order-dependent in the last bits only
@@ -977,11 +983,14 @@ template <int M_> static hipError_t launch_solve_m(const KParams &P, int B, cons
     hipLaunchKernelGGL((solve_kernel<M_, TPB>), dim3(B), dim3(TPB), 0, st, P, p, w0, w_out, obj, status, iters, kkt, ws);
     return hipGetLastError();
 }
-template <int M_> static hipError_t launch_eval_m(const KParams &P, int B, const double *p, const double *w, double *f, double *g, hipStream_t st)
+template <int M_> static hipError_t launch_eval_m(const KParams &P, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
 {
     if (f) { hipError_t e = hipMemsetAsync(f, 0, sizeof(double) * (size_t)B, st); if (e != hipSuccess) return e; }
     long total = (long)B * (P.N + 1);
-    hipLaunchKernelGGL((eval_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
+    if (ofield)
+        hipLaunchKernelGGL((eval_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
+    else
+        hipLaunchKernelGGL((eval_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
     return hipGetLastError();
 }
 template <int M_> static hipError_t launch_shift_m(const KParams &P, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st)
@@ -1096,9 +1105,9 @@ hipError_t launch_solve(const KParams &P, int m, int B, const double *p, const d
     NMPC_DISPATCH(m, C_)
 #undef C_
 }
-hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st)
+hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
 {
-#define C_(M) launch_eval_m<M>(P, B, p, w, f, g, st)
+#define C_(M) launch_eval_m<M>(P, B, p, w, f, g, st, ofield)
     NMPC_DISPATCH(m, C_)
 #undef C_
 }

@@ -84,6 +84,8 @@ constexpr int col_min_waves(int m, int thb, int dl)
     return m > 6 ? 1 : (m <= 3 ? NMPC_COL_WAVES_SMALL : (m == 4 ? NMPC_COL_WAVES_FOUR : ((m >= 5 && !thb && dl) ? NMPC_COL_WAVES_LAT : NMPC_COL_WAVES_MID)));
 }
 
+constexpr int NMPC_DL_OBS = 4;      // bit of the kernel's DL parameter: obstacle field from the per-instance array (see the kernel)
+
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 template <int N_> __device__ __forceinline__ void fmac_rowb(double &acc, double u, double nr)      // acc += u[lane N_ of my row of 16] * nr
 {
@@ -141,8 +143,11 @@ template <int M_, int THB> struct GC : G2<M_, THB> {
 // the stage-parallel phases (evaluation, optimality error, stage packs, step lengths, multipliers, merit function, update — 41 % of a lone
 // wave's iteration for six robots) and waits at a barrier while wave 0 runs the two sweeps; for batches whose launch is as long as their
 // longest solve.
+// DL: where the instance keeps its data, bits 0-1 (0 .. 3, see the slack / dual arrays below); bit 2 (NMPC_DL_OBS): the obstacle field is the
+// per-instance array of the *_obs entry points instead of the kernel argument (ObsField, nmpc_solve_common.h) — a separate instantiation, so
+// the plain ones carry no trace of it.
 template <int M_, int THB, int DL, int TPBK = 64>
-__global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_kernel(const KParams P, const double *__restrict__ p_in, const double *__restrict__ w0,
+__global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_col_kernel(const KParams P, const double *__restrict__ p_in, const double *__restrict__ w0,
                                                         double *__restrict__ w_out, double *__restrict__ obj_out,
                                                         int32_t *__restrict__ status_out, int32_t *__restrict__ iters_out,
                                                         double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
@@ -150,6 +155,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
     using G = GC<M_, THB>;
     constexpr int TPB = TPBK;
     static_assert(TPBK == 64 || TPBK == 128 || TPBK == 256, "one, two or four wavefronts per instance");
+    constexpr int DLL = DL & 3;            // data layout (the obstacle source bit apart)
     constexpr int NX = G::NX, NU = G::NU, NP = G::NP, NZ = G::NZ, LD = G::LD, NXB = G::NXB;
     constexpr int NPd = NP > 0 ? NP : 1;   // divisor that stays legal for M_ == 1 (those loops have zero trips)
     constexpr int MPN = M_ > 1 ? M_ - 1 : 1;   // partners of a robot in the pair rows
@@ -162,6 +168,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
     const int N = P.N, N1 = P.N + 1, K = P.K, MK = M_ * P.K;
     const double T = P.T;
     const size_t inst = (P.order && *P.order_bad == 0) ? (size_t)P.order[blockIdx.x] : (size_t)blockIdx.x;      // dispatch-order hint: long solves first (ignored unless it is a permutation)
+    const ObsField<DL / NMPC_DL_OBS> OB(P, inst);      // obstacle o at stage k: OB(k, o, c), c = 0 ox, 1 oy, 2 r — read by the instance, never the workgroup
     double mu = P.mu_init;                         // barrier parameter (declared here: the merit function of the elastic phase needs it)
     bool el = false;                               // elastic phase (the second restart of last resort): pair / obstacle rows h + t - s = 0 with penalty rho t
     const bool prs = P.pairs != 0;                 // pair rows present (the no-pair multi-robot NLP keeps NP slots that are never touched)
@@ -189,7 +196,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
     // The arrays are (wave-uniform base, uniform offset) pairs indexed by a 32-bit element index: the byte offset is formed in 32 bits and zero-extended,
     // which the compiler addresses as scalar base + 32-bit vector offset (`global_load v, v_off, s[base:base+1]`) instead of a 64-bit vector address
     // per access (two registers and two or three address instructions each).  NMPC_COL_SADDR = 0 keeps plain pointers (A/B).
-    double *gd = DL ? (RED + 8) : (ws + inst * P.stride2 + P.oDUAL);
+    double *gd = DLL ? (RED + 8) : (ws + inst * P.stride2 + P.oDUAL);
     const int oZPp = N1 * NP, oSO = oZPp + N1 * NP, oZO = oSO + N1 * MK, oZUL = oZO + N1 * MK, oZUU = oZUL + N * NU, oZXL = oZUU + N * NU, oZXU = oZXL + N1 * NXB,
               oSUL = oZXU + N1 * NXB, oSUU = oSUL + N * NU;
     const UArr SPp{gd, 0};                // [N1*NP]   pair slacks
@@ -205,9 +212,9 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
 
     // DL >= 2 (small teams, throughput shape): the stage factors — written by the backward sweep, read by the forward sweep — live in LDS as well, DL >= 3:
     // the stage packs too; otherwise both are in the instance's workspace (HBM/L2)
-    double *const dl_end = DL ? gd + oSUU + N * NU : RED + 8;
-    double *gkt = (DL >= 2) ? dl_end : ws + inst * P.stride2 + P.oKT;       // [N][KTS]
-    double *gpack = (DL >= 3) ? dl_end + (size_t)N * G::KTS : ws + inst * P.stride2 + P.oPACK;   // [N][PACK] + terminal [2*NX]
+    double *const dl_end = DLL ? gd + oSUU + N * NU : RED + 8;
+    double *gkt = (DLL >= 2) ? dl_end : ws + inst * P.stride2 + P.oKT;       // [N][KTS]
+    double *gpack = (DLL >= 3) ? dl_end + (size_t)N * G::KTS : ws + inst * P.stride2 + P.oPACK;   // [N][PACK] + terminal [2*NX]
     const UArr TPp{ws + inst * P.stride2 + P.oELAS, 0};           // [N1*NP]   elastic variables of the pair rows (elastic phase only; always in the workspace)
     const UArr TOb{ws + inst * P.stride2 + P.oELAS, N1 * NP};     // [N1*MK]   ... of the obstacle rows
     const double rho = P.rho_el;
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
 #ifdef NMPC_POISON
     {   // debug build: every LDS word and the instance's HBM workspace start as NMPC_POISON, so that a read of anything this solve did not
         // write shows up as a parity failure instead of depending on what ran on the CU before
-        const int nl = (int)((DL ? gd + oSUU + N * NU : RED + 8) - sm) + (DL >= 2 ? N * G::KTS : 0) + (DL >= 3 ? N1 * G::PACK : 0);
+        const int nl = (int)((DLL ? gd + oSUU + N * NU : RED + 8) - sm) + (DLL >= 2 ? N * G::KTS : 0) + (DLL >= 3 ? N1 * G::PACK : 0);
         for (int e = tid; e < nl; e += TPB) sm[e] = NMPC_POISON;
         for (size_t e = tid; e < (size_t)P.stride2; e += TPB) ws[inst * P.stride2 + e] = NMPC_POISON;
         __syncthreads();
@@ -280,8 +287,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
         }
         for (int e = tid; e < MK; e += TPB) {
             int i = e / K, o = e - i * K;
-            double dx = X[3 * i] - P.obs[3 * o], dy = X[3 * i + 1] - P.obs[3 * o + 1];
-            if (h_obs(r_obs(dx, dy), P.robdim, P.obs[3 * o + 2], P.margin) < -NMPC_X0_TOL) bad = 1.0;
+            double dx = X[3 * i] - OB(0, o, 0), dy = X[3 * i + 1] - OB(0, o, 1);
+            if (h_obs(r_obs(dx, dy), P.robdim, OB(0, o, 2), P.margin) < -NMPC_X0_TOL) bad = 1.0;
         }
         bad = wmax<TPB>(bad, RED);
         if (bad > 0.0) {
@@ -374,19 +381,19 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double px = X[oi] + a * DX[oi], py = X[oi + 1] + a * DX[oi + 1];
-            double h = h_obs(r_obs(px - P.obs[3 * o], py - P.obs[3 * o + 1]), P.robdim, P.obs[3 * o + 2], P.margin);
+            double h = h_obs(r_obs(px - OB(k, o, 0), py - OB(k, o, 1)), P.robdim, OB(k, o, 2), P.margin);
             double sv = SO[k * MK + e], tv = 0.0;
             if constexpr (EL) {
                 tv = TOb[k * MK + e];
                 if (a != 0.0) {
-                    double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey), ds, dz, dt;
-                    el_step(mu, rho, sv, ZO[k * MK + e], tv, h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]), ds, dz, dt);
+                    double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), ds, dz, dt;
+                    el_step(mu, rho, sv, ZO[k * MK + e], tv, h_obs(rr, P.robdim, OB(k, o, 2), P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]), ds, dz, dt);
                     sv += a * ds; tv += a * dt;
                 }
                 ls.add(tv); fs += rho * tv;
             } else if (a != 0.0) {
-                double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey);
-                sv += a * ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), sv);
+                double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey);
+                sv += a * ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
             }
             ls.add(sv);
             double r = fabs(h - sv + tv);
@@ -428,8 +435,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
             int k = it / MK, e = it - k * MK;
             if (k >= 1 && k <= N - 1) {
                 int i = e / K, o = e - i * K;
-                double dx = X[k * NX + 3 * i] - P.obs[3 * o], dy = X[k * NX + 3 * i + 1] - P.obs[3 * o + 1];
-                const double hv = h_obs(r_obs(dx, dy), P.robdim, P.obs[3 * o + 2], P.margin);
+                double dx = X[k * NX + 3 * i] - OB(k, o, 0), dy = X[k * NX + 3 * i + 1] - OB(k, o, 1);
+                const double hv = h_obs(r_obs(dx, dy), P.robdim, OB(k, o, 2), P.margin);
                 if (el) {
                     const double tv = fmax(bp, bp - hv), sv = hv + tv;
                     TOb[it] = tv; SO[it] = sv; ZO[it] = fmin(mu / sv, 0.5 * rho);
@@ -544,7 +551,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
                     });
                 }
                 for (int o = 0; o < K; o++) {
-                    double dx = xi - P.obs[3 * o], dy = yi - P.obs[3 * o + 1], rr = r_obs(dx, dy), z = ZO[kk * MK + i * K + o];
+                    double dx = xi - OB(kk, o, 0), dy = yi - OB(kk, o, 1), rr = r_obs(dx, dy), z = ZO[kk * MK + i * K + o];
                     j0 += qdiv(dx, rr) * z; j1 += qdiv(dy, rr) * z;
                 }
             }
@@ -658,10 +665,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
                         });
                     }
                     for (int o = 0; o < K; o++) {
-                        double dx = xi - P.obs[3 * o], dy = yi - P.obs[3 * o + 1], rr = r_obs(dx, dy), n0 = qdiv(dx, rr), n1 = qdiv(dy, rr);
+                        double dx = xi - OB(k, o, 0), dy = yi - OB(k, o, 1), rr = r_obs(dx, dy), n0 = qdiv(dx, rr), n1 = qdiv(dy, rr);
                         double sv = SO[k * MK + i * K + o], zv = ZO[k * MK + i * K + o], sg, v, zz = qdiv(zv, rr);
-                        if constexpr (EL) el_sigma(mu, rho, sv, zv, TOb[k * MK + i * K + o], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), sg, v);
-                        else { sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin) - sv); }
+                        if constexpr (EL) el_sigma(mu, rho, sv, zv, TOb[k * MK + i * K + o], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sg, v);
+                        else { sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_obs(rr, P.robdim, OB(k, o, 2), P.margin) - sv); }
                         g0 -= n0 * v; g1 -= n1 * v;
                         h0 += sg * n0 * n0 - zz * (1 - n0 * n0); hxy += sg * n0 * n1 + zz * n0 * n1; h1 += sg * n1 * n1 - zz * (1 - n1 * n1);
                     }
@@ -1321,8 +1328,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
         for (int it = tid; it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
-            double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey), sv = SO[k * MK + e];
-            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), sv);
+            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e];
+            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
             mult_max = fmax(mult_max, fabs(fb(sv, ZO[k * MK + e], ds)));
         }
         } else {        // elastic phase: the same two loops over elastic rows
@@ -1336,8 +1343,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
         for (int it = tid; it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
-            double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey);
-            mult_max = fmax(mult_max, fabs(fbe(SO[k * MK + e], ZO[k * MK + e], TOb[k * MK + e], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]))));
+            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey);
+            mult_max = fmax(mult_max, fabs(fbe(SO[k * MK + e], ZO[k * MK + e], TOb[k * MK + e], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]))));
         }
         }
         a_p = wmin<TPB>(a_p, RED); a_d = wmin<TPB>(a_d, RED);
@@ -1385,16 +1392,16 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
                     });
                 }
                 for (int o = 0; o < K; o++) {
-                    double ex = xi - P.obs[3 * o], ey = yi - P.obs[3 * o + 1], rr = r_obs(ex, ey), n0 = qdiv(ex, rr), n1 = qdiv(ey, rr);
+                    double ex = xi - OB(k, o, 0), ey = yi - OB(k, o, 1), rr = r_obs(ex, ey), n0 = qdiv(ex, rr), n1 = qdiv(ey, rr);
                     double sv = SO[k * MK + i * K + o], zv = ZO[k * MK + i * K + o];
                     double nd = n0 * dx[3 * i] + n1 * dx[3 * i + 1];
                     double znew, zz = qdiv(zv, rr);
                     if constexpr (EL) {
                         double ds, dz, dt;
-                        el_step(mu, rho, sv, zv, TOb[k * MK + i * K + o], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), jd_obs(ex, ey, rr, dx[3 * i], dx[3 * i + 1]), ds, dz, dt);
+                        el_step(mu, rho, sv, zv, TOb[k * MK + i * K + o], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), jd_obs(ex, ey, rr, dx[3 * i], dx[3 * i + 1]), ds, dz, dt);
                         znew = zv + dz;
                     } else {
-                    double ds = ds_obs(ex, ey, rr, dx[3 * i], dx[3 * i + 1], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), sv);
+                    double ds = ds_obs(ex, ey, rr, dx[3 * i], dx[3 * i + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
                     znew = zv + dz_of(mu, sv, zv, ds);
                     }
                     l0 += n0 * znew + zz * (dx[3 * i] - n0 * nd);
@@ -1482,8 +1489,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
         for (int it = tid; it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
-            double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey), sv = SO[k * MK + e];
-            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), sv);
+            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e];
+            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
             dphi -= mu * ds / sv;
         }
 #endif
@@ -1572,8 +1579,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
         for (int it = tid; it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
-            double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey), sv = SO[k * MK + e], sn;
-            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), sv);
+            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e], sn;
+            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
             ZO[k * MK + e] = zup(sv, ZO[k * MK + e], ds, sn);
             SO[k * MK + e] = sn;
         }
@@ -1589,8 +1596,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL)) void solve_col_ke
         for (int it = tid; it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
-            double ex = X[oi] - P.obs[3 * o], ey = X[oi + 1] - P.obs[3 * o + 1], rr = r_obs(ex, ey), sn, tn;
-            ZO[k * MK + e] = zupe(SO[k * MK + e], ZO[k * MK + e], TOb[k * MK + e], h_obs(rr, P.robdim, P.obs[3 * o + 2], P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]), sn, tn);
+            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sn, tn;
+            ZO[k * MK + e] = zupe(SO[k * MK + e], ZO[k * MK + e], TOb[k * MK + e], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]), sn, tn);
             SO[k * MK + e] = sn; TOb[k * MK + e] = tn;
         }
         }
@@ -1672,9 +1679,11 @@ template <int M_, int THB> static int col_factor_mode(const KParams &P)
     return col_lds_bytes<M_, THB>(P, true, NMPC_COL_FL_MODE) <= NMPC_COL_FL_BYTES ? NMPC_COL_FL_MODE : 0;
 }
 
-template <int M_, int THB> static hipError_t launch3_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
+// OBS = 1: the instantiations of the per-instance obstacle field (P.ofield), in the same shapes and data layouts as the plain ones
+template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
                                                         int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape)
 {
+    constexpr int OB = OBS ? NMPC_DL_OBS : 0;
     constexpr int DLmax = (M_ <= NMPC_COL_DL_MAXM) ? 1 : 0;
     // latency shape (two wavefronts per instance): slacks and duals in LDS up to six robots — occupancy is not what a launch that lasts as
     // long as its longest solve is short of — and in the workspace for eight and ten
@@ -1689,7 +1698,9 @@ template <int M_, int THB> static hipError_t launch3_mt(const KParams &P, int B,
     // obstacles: composite B=1024 28.7 k -> 33.5 k solves/s; six robots without obstacles B=512 42.3 k -> 43.4 k) and the build time counts
     constexpr int TPB4 = (M_ == 5 || M_ == 6) ? 256 : 128;
     if (shape == 2 && TPB4 == 128) shape = 1;
-    auto kern = shape == 2 ? solve_col_kernel<M_, THB, DLlat, TPB4> : (lat ? solve_col_kernel<M_, THB, DLlat, 128> : (fl ? solve_col_kernel<M_, THB, DLmax * FLM, 64> : (dl ? solve_col_kernel<M_, THB, DLmax, 64> : solve_col_kernel<M_, THB, 0, 64>)));
+    auto kern = shape == 2 ? solve_col_kernel<M_, THB, DLlat | OB, TPB4>
+                           : (lat ? solve_col_kernel<M_, THB, DLlat | OB, 128>
+                                  : (fl ? solve_col_kernel<M_, THB, DLmax * FLM | OB, 64> : (dl ? solve_col_kernel<M_, THB, DLmax | OB, 64> : solve_col_kernel<M_, THB, OB, 64>)));
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1697,27 +1708,28 @@ template <int M_, int THB> static hipError_t launch3_mt(const KParams &P, int B,
     hipLaunchKernelGGL(kern, dim3(B), dim3(shape == 2 ? 256 : (lat ? 128 : 64)), lds, st, P, p, w0, w_out, obj, status, iters, kkt, ws, prof);
     return hipGetLastError();
 }
-template <int M_> static hipError_t launch3_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                                              int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape)
+template <int M_, int OBS> static hipError_t launch3_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
+                                                       int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape)
 {
-    return P.thb ? launch3_mt<M_, 1>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape)
-                 : launch3_mt<M_, 0>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
+    return P.thb ? launch3_mt<M_, 1, OBS>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape)
+                 : launch3_mt<M_, 0, OBS>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
 }
 
-// The team sizes are instantiated in up to three objects so that the build spreads over the cores (one hipcc -c per part, see build.py;
+// The team sizes are instantiated in up to six objects so that the build spreads over the cores (one hipcc -c per part, see build.py;
 // the ten team sizes take ~350 s in one translation unit): NMPC_COL_PART 0 = everything here (variants, NMPC_COL_ONLY_M), 1 = the entry
-// points below plus 1..5 robots, 2 = 6..8 robots, 3 = 9..10 robots.
+// points below plus 1..5 robots, 2 = 6..8 robots, 3 = 9..10 robots; 4, 5, 6 = the same team sizes for the per-instance obstacle field.
 #ifndef NMPC_COL_PART
 #define NMPC_COL_PART 0
 #endif
 #define COL_ARGS_DECL const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status, int32_t *iters, \
                       double *kkt, double *ws, long long *prof, hipStream_t st, int shape
-#define COL_CASE(M) case M: return launch3_m<M>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
+#define COL_ARGS P, m, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape
+#define COL_CASE(M, OBS) case M: return launch3_m<M, OBS>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
 #if NMPC_COL_PART == 2
 hipError_t launch_solve_col_part2(COL_ARGS_DECL)
 {
     switch (m) {
-        COL_CASE(6) COL_CASE(7) COL_CASE(8)
+        COL_CASE(6, 0) COL_CASE(7, 0) COL_CASE(8, 0)
     default: return hipErrorInvalidValue;
     }
 }
@@ -1725,7 +1737,31 @@ hipError_t launch_solve_col_part2(COL_ARGS_DECL)
 hipError_t launch_solve_col_part3(COL_ARGS_DECL)
 {
     switch (m) {
-        COL_CASE(9) COL_CASE(10)
+        COL_CASE(9, 0) COL_CASE(10, 0)
+    default: return hipErrorInvalidValue;
+    }
+}
+#elif NMPC_COL_PART == 4
+hipError_t launch_solve_col_obs_part1(COL_ARGS_DECL)
+{
+    switch (m) {
+        COL_CASE(1, 1) COL_CASE(2, 1) COL_CASE(3, 1) COL_CASE(4, 1) COL_CASE(5, 1)
+    default: return hipErrorInvalidValue;
+    }
+}
+#elif NMPC_COL_PART == 5
+hipError_t launch_solve_col_obs_part2(COL_ARGS_DECL)
+{
+    switch (m) {
+        COL_CASE(6, 1) COL_CASE(7, 1) COL_CASE(8, 1)
+    default: return hipErrorInvalidValue;
+    }
+}
+#elif NMPC_COL_PART == 6
+hipError_t launch_solve_col_obs_part3(COL_ARGS_DECL)
+{
+    switch (m) {
+        COL_CASE(9, 1) COL_CASE(10, 1)
     default: return hipErrorInvalidValue;
     }
 }
@@ -1733,21 +1769,40 @@ hipError_t launch_solve_col_part3(COL_ARGS_DECL)
 #if NMPC_COL_PART == 1
 hipError_t launch_solve_col_part2(COL_ARGS_DECL);
 hipError_t launch_solve_col_part3(COL_ARGS_DECL);
+hipError_t launch_solve_col_obs_part1(COL_ARGS_DECL);
+hipError_t launch_solve_col_obs_part2(COL_ARGS_DECL);
+hipError_t launch_solve_col_obs_part3(COL_ARGS_DECL);
 #endif
 // shape: 0 = throughput (one wavefront per instance), 1 / 2 = latency (two / four wavefronts per instance, see the kernel)
 hipError_t launch_solve_col(COL_ARGS_DECL)
 {
     switch (m) {
 #ifdef NMPC_COL_ONLY_M
-        COL_CASE(NMPC_COL_ONLY_M)
+        COL_CASE(NMPC_COL_ONLY_M, 0)
 #else
-        COL_CASE(1) COL_CASE(2) COL_CASE(3) COL_CASE(4) COL_CASE(5)
+        COL_CASE(1, 0) COL_CASE(2, 0) COL_CASE(3, 0) COL_CASE(4, 0) COL_CASE(5, 0)
 #if NMPC_COL_PART == 1
-    case 6: case 7: case 8: return launch_solve_col_part2(P, m, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
-    case 9: case 10: return launch_solve_col_part3(P, m, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
+    case 6: case 7: case 8: return launch_solve_col_part2(COL_ARGS);
+    case 9: case 10: return launch_solve_col_part3(COL_ARGS);
 #else
-        COL_CASE(6) COL_CASE(7) COL_CASE(8) COL_CASE(9) COL_CASE(10)
+        COL_CASE(6, 0) COL_CASE(7, 0) COL_CASE(8, 0) COL_CASE(9, 0) COL_CASE(10, 0)
 #endif
+#endif
+    default: return hipErrorInvalidValue;
+    }
+}
+// the same with the per-instance obstacle field P.ofield
+hipError_t launch_solve_col_obs(COL_ARGS_DECL)
+{
+    switch (m) {
+#ifdef NMPC_COL_ONLY_M
+        COL_CASE(NMPC_COL_ONLY_M, 1)
+#elif NMPC_COL_PART == 1
+    case 1: case 2: case 3: case 4: case 5: return launch_solve_col_obs_part1(COL_ARGS);
+    case 6: case 7: case 8: return launch_solve_col_obs_part2(COL_ARGS);
+    case 9: case 10: return launch_solve_col_obs_part3(COL_ARGS);
+#else
+        COL_CASE(1, 1) COL_CASE(2, 1) COL_CASE(3, 1) COL_CASE(4, 1) COL_CASE(5, 1) COL_CASE(6, 1) COL_CASE(7, 1) COL_CASE(8, 1) COL_CASE(9, 1) COL_CASE(10, 1)
 #endif
     default: return hipErrorInvalidValue;
     }
@@ -1766,6 +1821,7 @@ size_t col_kernel_bytes(const KParams &P, int m, int shape)
 
 #endif      // NMPC_COL_PART
 #undef COL_CASE
+#undef COL_ARGS
 #undef COL_ARGS_DECL
 
 }  // namespace nmpc

@@ -39,6 +39,28 @@ template <int M_, int THB> struct G2 {
     static constexpr int KTS = ((NU * LD + NU > NU * LDC ? NU * LD + NU : NU * LDC) + 7) / 8 * 8;
 };
 
+// ---- the obstacle field: component c (0 ox, 1 oy, 2 r) of obstacle o as the obstacle rows of stage k (evaluated at X_k) of one instance see
+// it.  Every obstacle read of the solve and evaluation kernels goes through here; where the field comes from is a compile-time choice of the
+// instantiation, never a run-time branch:
+//   OS = 0  the handle's config field P.obs, a kernel argument shared by every instance and stage (nmpc_solve_batch and its kin);
+//   OS = 1  the per-instance field of the *_obs entry points, P.ofield.ptr [B][S][K][3] in device memory: the instance's base is wave-uniform
+//           (scalar registers), the element offset a 32-bit index (saddr addressing); the stage stride is 0 for a static field (S = 1).
+template <int OS> struct ObsField {
+    const KParams &P;
+    const double *f;      // OS = 1: the instance's [S][K][3]
+    __device__ __forceinline__ ObsField(const KParams &P_, size_t inst) : P(P_), f(nullptr)
+    {
+        if constexpr (OS != 0) f = P_.ofield.ptr + inst * (size_t)P_.ofield.istride;
+    }
+    __device__ __forceinline__ double operator()(int k, int o, int c) const
+    {
+        if constexpr (OS != 0)
+            return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(f) + (size_t)((uint32_t)(k * P.ofield.sstride + 3 * o + c) * 8u));
+        else
+            return P.obs[3 * o + c];
+    }
+};
+
 // ---- single evaluation points.  Constraint values, slack steps and defects are recomputed at several places of an
 // iteration (Newton right-hand side, step-size rule, multiplier recursion, update).  With sigma = z/s up to 1e13 a
 // last-bit difference between two sites (e.g. a differently contracted a*b+c) shows up as 1e-7 in the dual residual, so

@@ -132,24 +132,49 @@ class NmpcSolver:
         t = self.torch.as_tensor(a, dtype=self.torch.float64, device=self.device).reshape(shape).contiguous()
         return t
 
+    def _obstacles(self, obstacles, B):
+        """The per-instance obstacle field of a call: [B, K, 3] (static, S = 1) or [B, N, K, 3] (entry k: the obstacles at the time of X_k, S = N),
+        K = len(cfg.obstacles) > 0, (ox, oy, r) per obstacle -> (contiguous float64 device tensor [B, S, K, 3], S)."""
+        K, N = len(self.cfg.obstacles), self.cfg.N
+        if K == 0:
+            raise ValueError("obstacles= needs a handle with obstacle rows: a config with K entries in `obstacles` (they are the default field)")
+        o = self.torch.as_tensor(obstacles, dtype=self.torch.float64, device=self.device)
+        if o.dim() == 3 and tuple(o.shape) == (B, K, 3):
+            o = o.reshape(B, 1, K, 3)
+        elif not (o.dim() == 4 and tuple(o.shape) in ((B, N, K, 3), (B, 1, K, 3))):      # [B, 1, K, 3]: the C ABI's S = 1
+            raise ValueError(f"obstacles must have shape ({B}, {K}, 3) or ({B}, {N}, {K}, 3), got {tuple(o.shape)}")
+        return o.contiguous(), int(o.shape[1])
+
     # ---- batched device API -----------------------------------------------------------------
-    def solve_batch(self, p, w0, want_fg: bool = False, order=None):
+    def solve_batch(self, p, w0, want_fg: bool = False, order=None, obstacles=None):
         """p [B, 2 n_x], w0 [B, n_var] (torch cuda / numpy) -> dict of torch cuda tensors.
 
         order: optional permutation of range(B) (dispatch-order hint, nmpc_solve_batch_ordered): workgroup g solves instance
-        order[g]; put the instances expected to need the most iterations first.  Results are unaffected."""
+        order[g]; put the instances expected to need the most iterations first.  Results are unaffected.
+        obstacles: optional per-instance obstacle field (nmpc_solve_batch_obs), [B, K, 3] static or [B, N, K, 3] per stage (entry k: the
+        obstacles at the time of X_k), K = len(cfg.obstacles); the config's coordinates are then not used."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w0 = self._dev(w0, (B, self.n_var))
         if B > self.max_batch:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
         w = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
         obj = torch.empty(B, dtype=torch.float64, device=self.device)
         kkt = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device)
         iters = torch.empty(B, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            if order is None:
+            if ob is not None:
+                od = None
+                if order is not None:
+                    od = torch.as_tensor(order, device=self.device).to(torch.int32).contiguous()
+                    if od.shape != (B,):
+                        raise ValueError(f"order must have shape ({B},)")
+                _lib.check(self.lib.nmpc_solve_batch_obs(self._h, B, p.data_ptr(), ob[0].data_ptr(), ob[1], w0.data_ptr(), w.data_ptr(), obj.data_ptr(),
+                                                         status.data_ptr(), iters.data_ptr(), kkt.data_ptr(), od.data_ptr() if od is not None else None,
+                                                         self._stream()), "nmpc_solve_batch_obs")
+            elif order is None:
                 _lib.check(self.lib.nmpc_solve_batch(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(),
                                                      status.data_ptr(), iters.data_ptr(), kkt.data_ptr(), self._stream()), "nmpc_solve_batch")
             else:
@@ -160,15 +185,16 @@ class NmpcSolver:
                                                              iters.data_ptr(), kkt.data_ptr(), od.data_ptr(), self._stream()), "nmpc_solve_batch_ordered")
         out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt)
         if want_fg:
-            f, g = self.eval_batch(p, w)
+            f, g = self.eval_batch(p, w, obstacles=ob[0] if ob is not None else None)
             out["f"], out["g"] = f, g
         return out
 
-    def step_batch(self, p, w, order=None):
+    def step_batch(self, p, w, order=None, obstacles=None):
         """One control period on the device (nmpc_step_batch): solve from the guess w, then IN PLACE w <- shifted solution and
         p[:, :n_x] <- x0 + T f(x0, u_0); `order` [B] int32 device tensor (in: dispatch order of this period, out: the order for the
         next one, sorted by this period's iteration counts, longest first) or None.  p and w must be contiguous float64 device
-        tensors owned by the caller (they are modified).  Returns sol['x'] of this period and the per-instance outputs."""
+        tensors owned by the caller (they are modified).  Returns sol['x'] of this period and the per-instance outputs.
+        obstacles: optional per-instance obstacle field of this period (nmpc_step_batch_obs), as in solve_batch."""
         torch = self.torch
         B = p.shape[0]
         if not (torch.is_tensor(p) and torch.is_tensor(w) and p.is_cuda and w.is_cuda and p.dtype == torch.float64 and w.dtype == torch.float64
@@ -178,21 +204,33 @@ class NmpcSolver:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
         if order is not None and not (torch.is_tensor(order) and order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.shape == (B,)):
             raise ValueError("order must be a contiguous int32 device tensor of shape (B,)")
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
         x = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
         obj = torch.empty(B, dtype=torch.float64, device=self.device); kkt = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device); iters = torch.empty(B, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
+            if ob is not None:
+                _lib.check(self.lib.nmpc_step_batch_obs(self._h, B, p.data_ptr(), w.data_ptr(), x.data_ptr(), ob[0].data_ptr(), ob[1], obj.data_ptr(),
+                                                        status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
+                                                        order.data_ptr() if order is not None else None, self._stream()), "nmpc_step_batch_obs")
+                return dict(x=x, f=obj, status=status, iters=iters, kkt=kkt, order=order)
             _lib.check(self.lib.nmpc_step_batch(self._h, B, p.data_ptr(), w.data_ptr(), x.data_ptr(), obj.data_ptr(), status.data_ptr(), iters.data_ptr(),
                                                 kkt.data_ptr(), order.data_ptr() if order is not None else None, self._stream()), "nmpc_step_batch")
         return dict(x=x, f=obj, status=status, iters=iters, kkt=kkt, order=order)
 
-    def eval_batch(self, p, w):
+    def eval_batch(self, p, w, obstacles=None):
+        """f [B] and g [B, n_g] at w (nmpc_eval_batch); obstacles: optional per-instance obstacle field (nmpc_eval_batch_obs), as in solve_batch."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w = self._dev(w, (B, self.n_var))
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
         f = torch.empty(B, dtype=torch.float64, device=self.device)
         g = torch.empty((B, self.n_g), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
+            if ob is not None:
+                _lib.check(self.lib.nmpc_eval_batch_obs(self._h, B, p.data_ptr(), w.data_ptr(), ob[0].data_ptr(), ob[1], f.data_ptr(), g.data_ptr(),
+                                                        self._stream()), "nmpc_eval_batch_obs")
+                return f, g
             _lib.check(self.lib.nmpc_eval_batch(self._h, B, p.data_ptr(), w.data_ptr(), f.data_ptr(), g.data_ptr(), self._stream()), "nmpc_eval_batch")
         return f, g
 
@@ -290,8 +328,12 @@ class PipelinedSolver:
         sol = self.solvers[k]
         p = sol._dev(p, (-1, sol.n_p))                       # on the caller's stream (a host array is copied there)
         w0 = sol._dev(w0, (p.shape[0], sol.n_var))
+        if kw.get("obstacles") is not None:
+            kw["obstacles"] = sol._obstacles(kw["obstacles"], p.shape[0])[0]      # the field too: [B, S, K, 3] on the device
         st.wait_stream(torch.cuda.current_stream(self.device))
         p.record_stream(st); w0.record_stream(st)            # the caller may drop its references at once: the allocator must not hand the inputs out again before the solve has read them
+        if kw.get("obstacles") is not None:
+            kw["obstacles"].record_stream(st)
         with torch.cuda.stream(st):
             r = sol.solve_batch(p, w0, **kw)
             ev = torch.cuda.Event()
