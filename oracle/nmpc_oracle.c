@@ -78,6 +78,9 @@ typedef struct {
     int pi[NMPC_MAX_ROBOTS * (NMPC_MAX_ROBOTS - 1) / 2], pj[NMPC_MAX_ROBOTS * (NMPC_MAX_ROBOTS - 1) / 2];
     int bidx[NXM]; /* bounded-state slot -> state index */
     double obs[3 * NMPC_MAX_OBSTACLES];
+    const double *fld;  /* obstacle field of the instance being solved: entry k at fld + k * fstride, (ox, oy, r) per obstacle.  The plain calls
+                           point it at obs with stride 0; the *_obs calls at the instance's [S][K][3] block (stride 3 K for S = N, 0 for S = 1) */
+    int fstride;
     double tol, mu_init;
     int max_iter;
     /* iterate + step */
@@ -132,6 +135,7 @@ static ws_t *ws_new(const nmpc_config_t *c)
     w->tol = c->tol; w->mu_init = c->mu_init; w->max_iter = c->max_iter;
     if (w->ipopt && c->mu_init == 0.5) w->mu_init = 0.1;      /* IPOPT's default where the caller did not choose */
     memcpy(w->obs, c->obs, sizeof(w->obs));
+    w->fld = w->obs; w->fstride = 0;
     for (int i = 0; i < m; i++) {
         for (int d = 0; d < 3; d++) w->qd[3 * i + d] = c->q[d];
         for (int d = 0; d < 2; d++) w->rd[2 * i + d] = c->r[d];
@@ -170,6 +174,9 @@ static void ws_free(ws_t *w)
     free(w);
 }
 
+/* obstacle o at stage k (the time of X_k): (ox, oy, r) */
+static inline const double *obs_at(const ws_t *w, int k, int o) { return w->fld + (size_t)k * w->fstride + 3 * o; }
+
 /* which inequality slots exist at stage k: u rows k<N; x-bound rows k>=1; pair/obstacle rows 1<=k<=N-1 */
 static inline int slot_active(const ws_t *w, int k, int s)
 {
@@ -194,8 +201,9 @@ static void stage_h(const ws_t *w, int k, const double *x, const double *u, doub
         }
         for (int i = 0; i < w->m; i++)
             for (int o = 0; o < w->K; o++) {
-                double dx = x[3 * i] - w->obs[3 * o], dy = x[3 * i + 1] - w->obs[3 * o + 1];
-                h[w->o_ob + i * w->K + o] = sqrt(dx * dx + dy * dy) - w->robdim - w->obs[3 * o + 2] - w->margin;
+                const double *ob = obs_at(w, k, o);
+                double dx = x[3 * i] - ob[0], dy = x[3 * i + 1] - ob[1];
+                h[w->o_ob + i * w->K + o] = sqrt(dx * dx + dy * dy) - w->robdim - ob[2] - w->margin;
             }
     }
 }
@@ -213,7 +221,8 @@ static void jxT_apply(const ws_t *w, int k, const double *x, const double *v, do
         }
         for (int i = 0; i < w->m; i++)
             for (int o = 0; o < w->K; o++) {
-                double dx = x[3 * i] - w->obs[3 * o], dy = x[3 * i + 1] - w->obs[3 * o + 1];
+                const double *ob = obs_at(w, k, o);
+                double dx = x[3 * i] - ob[0], dy = x[3 * i + 1] - ob[1];
                 double rr = sqrt(dx * dx + dy * dy), z = v[w->o_ob + i * w->K + o];
                 out[3 * i] += dx / rr * z; out[3 * i + 1] += dy / rr * z;
             }
@@ -236,7 +245,8 @@ static void j_apply(const ws_t *w, int k, const double *x, const double *dx_, co
         }
         for (int i = 0; i < w->m; i++)
             for (int o = 0; o < w->K; o++) {
-                double dx = x[3 * i] - w->obs[3 * o], dy = x[3 * i + 1] - w->obs[3 * o + 1];
+                const double *ob = obs_at(w, k, o);
+                double dx = x[3 * i] - ob[0], dy = x[3 * i + 1] - ob[1];
                 double rr = sqrt(dx * dx + dy * dy);
                 out[w->o_ob + i * w->K + o] = (dx * dx_[3 * i] + dy * dx_[3 * i + 1]) / rr;
             }
@@ -449,8 +459,9 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
     }
     for (int i = 0; i < m; i++)
         for (int o = 0; o < w->K; o++) {
-            double dx = x0p[3 * i] - w->obs[3 * o], dy = x0p[3 * i + 1] - w->obs[3 * o + 1];
-            if (sqrt(dx * dx + dy * dy) - w->robdim - w->obs[3 * o + 2] < w->margin - NMPC_X0_TOL) infeasible = 1;
+            const double *ob = obs_at(w, 0, o);
+            double dx = x0p[3 * i] - ob[0], dy = x0p[3 * i + 1] - ob[1];
+            if (sqrt(dx * dx + dy * dy) - w->robdim - ob[2] < w->margin - NMPC_X0_TOL) infeasible = 1;
         }
     if (infeasible) {
         memcpy(wout, w->X, sizeof(double) * (size_t)(N + 1) * nx);
@@ -608,7 +619,8 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
                     }
                     for (int i = 0; i < m; i++)
                         for (int o = 0; o < w->K; o++) {
-                            double dx = x[3 * i] - w->obs[3 * o], dy = x[3 * i + 1] - w->obs[3 * o + 1];
+                            const double *ob = obs_at(w, k, o);
+                            double dx = x[3 * i] - ob[0], dy = x[3 * i + 1] - ob[1];
                             double rr = sqrt(dx * dx + dy * dy), n0 = dx / rr, n1 = dy / rr;
                             int sl = w->o_ob + i * w->K + o;
                             double sg = sige[sl], zz = z[sl] / rr;
@@ -1007,11 +1019,14 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
 
 /* ---- exported test/baseline entry points ------------------------------------------------- */
 
-int32_t nmpc_oracle_solve_batch(const nmpc_config_t *cfg, int32_t B, const double *p, const double *w0, double *w_out, double *obj,
-                                int32_t *status, int32_t *iters, double *kkt, int32_t nthreads)
+/* obs == NULL: the config's field for every instance; otherwise instance b reads the [S][K][3] block obs + b S K 3 (S = 1: one entry for every
+   stage; S = N: entry k at stage k), as nmpc_solve_batch_obs / nmpc_eval_batch_obs of include/nmpc.h */
+static int32_t solve_batch_field(const nmpc_config_t *cfg, int32_t B, const double *p, const double *obs, int32_t S, const double *w0, double *w_out,
+                                 double *obj, int32_t *status, int32_t *iters, double *kkt, int32_t nthreads)
 {
     if (!cfg || cfg->m < 1 || cfg->m > NMPC_MAX_ROBOTS || cfg->N < 1 || cfg->n_obs < 0 || cfg->n_obs > NMPC_MAX_OBSTACLES) return NMPC_E_ARG;
     const int nv = nmpc_oracle_n_var(cfg), np_ = nmpc_oracle_n_p(cfg);
+    const size_t fsz = (size_t)S * 3 * cfg->n_obs;
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #else
@@ -1023,6 +1038,7 @@ int32_t nmpc_oracle_solve_batch(const nmpc_config_t *cfg, int32_t B, const doubl
 #pragma omp for schedule(dynamic, 1)
         for (int b = 0; b < B; b++) {
             double o = 0, k = 0; int it = 0;
+            if (obs) { w->fld = obs + (size_t)b * fsz; w->fstride = S > 1 ? 3 * cfg->n_obs : 0; }
             int st = solve_one(w, p + (size_t)b * np_, w0 + (size_t)b * nv, w_out + (size_t)b * nv, &o, &it, &k);
             if (obj) obj[b] = o;
             if (status) status[b] = st;
@@ -1034,8 +1050,28 @@ int32_t nmpc_oracle_solve_batch(const nmpc_config_t *cfg, int32_t B, const doubl
     return NMPC_OK;
 }
 
-/* f and g in the reference's row order (C6:278,314,318-331) */
-int32_t nmpc_oracle_eval_batch(const nmpc_config_t *cfg, int32_t B, const double *p, const double *wv, double *f, double *g)
+int32_t nmpc_oracle_solve_batch(const nmpc_config_t *cfg, int32_t B, const double *p, const double *w0, double *w_out, double *obj,
+                                int32_t *status, int32_t *iters, double *kkt, int32_t nthreads)
+{
+    return solve_batch_field(cfg, B, p, NULL, 0, w0, w_out, obj, status, iters, kkt, nthreads);
+}
+
+/* the argument rules of the *_obs calls (include/nmpc.h): obstacle rows, a field, S = 1 or N */
+static int field_args_ok(const nmpc_config_t *cfg, int32_t B, const double *obs, int32_t S)
+{
+    return cfg && cfg->n_obs > 0 && (obs || B <= 0) && (S == 1 || S == cfg->N);
+}
+
+int32_t nmpc_oracle_solve_batch_obs(const nmpc_config_t *cfg, int32_t B, const double *p, const double *obs, int32_t S, const double *w0,
+                                    double *w_out, double *obj, int32_t *status, int32_t *iters, double *kkt, int32_t nthreads)
+{
+    if (!field_args_ok(cfg, B, obs, S)) return NMPC_E_ARG;
+    return solve_batch_field(cfg, B, p, obs, S, w0, w_out, obj, status, iters, kkt, nthreads);
+}
+
+/* f and g in the reference's row order (C6:278,314,318-331); field as in solve_batch_field (stage k's obstacle rows, at X_k, read entry k) */
+static int32_t eval_batch_field(const nmpc_config_t *cfg, int32_t B, const double *p, const double *wv, const double *obs, int32_t S, double *f,
+                                double *g)
 {
     const int m = cfg->m, N = cfg->N, nx = 3 * m, nu = 2 * m, M = cfg->pair_rows ? m * (m - 1) / 2 : 0, K = cfg->n_obs;
     const int nv = nmpc_oracle_n_var(cfg), ng = nmpc_oracle_n_g(cfg);
@@ -1050,6 +1086,7 @@ int32_t nmpc_oracle_eval_batch(const nmpc_config_t *cfg, int32_t B, const double
         }
         for (int k = 0; k < N; k++) {
             const double *x = X + (size_t)k * nx, *xn = x + nx, *u = U + (size_t)k * nu;
+            const double *ob = obs ? obs + ((size_t)b * S + (S > 1 ? k : 0)) * 3 * K : cfg->obs;
             for (int i = 0; i < m; i++) {
                 for (int d = 0; d < 3; d++) { double e = x[3 * i + d] - pp[nx + 3 * i + d]; fv += cfg->q[d] * e * e; }
                 fv += cfg->r[0] * u[2 * i] * u[2 * i] + cfg->r[1] * u[2 * i + 1] * u[2 * i + 1];
@@ -1067,14 +1104,26 @@ int32_t nmpc_oracle_eval_batch(const nmpc_config_t *cfg, int32_t B, const double
                     }
                 for (int i = 0; i < m; i++)
                     for (int q = 0; q < K; q++) {
-                        double dx = x[3 * i] - cfg->obs[3 * q], dy = x[3 * i + 1] - cfg->obs[3 * q + 1];
-                        gg[o++] = sqrt(dx * dx + dy * dy) - cfg->rob_dim - cfg->obs[3 * q + 2];
+                        double dx = x[3 * i] - ob[3 * q], dy = x[3 * i + 1] - ob[3 * q + 1];
+                        gg[o++] = sqrt(dx * dx + dy * dy) - cfg->rob_dim - ob[3 * q + 2];
                     }
             }
         }
         if (f) f[b] = fv;
     }
     return NMPC_OK;
+}
+
+int32_t nmpc_oracle_eval_batch(const nmpc_config_t *cfg, int32_t B, const double *p, const double *wv, double *f, double *g)
+{
+    return eval_batch_field(cfg, B, p, wv, NULL, 0, f, g);
+}
+
+int32_t nmpc_oracle_eval_batch_obs(const nmpc_config_t *cfg, int32_t B, const double *p, const double *wv, const double *obs, int32_t S, double *f,
+                                   double *g)
+{
+    if (!field_args_ok(cfg, B, obs, S)) return NMPC_E_ARG;
+    return eval_batch_field(cfg, B, p, wv, obs, S, f, g);
 }
 
 /* warm-start shift (C6:160-169,460-465) and optional plant step (casadi_test.py:17-26) */

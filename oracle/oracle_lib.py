@@ -41,6 +41,10 @@ def lib():
         _LIB.nmpc_oracle_solve_batch.argtypes = [C.POINTER(Config), C.c_int32, dp, dp, dp, dp, ip, ip, dp, C.c_int32]
         _LIB.nmpc_oracle_solve_batch.restype = C.c_int32
         _LIB.nmpc_oracle_eval_batch.argtypes = [C.POINTER(Config), C.c_int32, dp, dp, dp, dp]
+        _LIB.nmpc_oracle_solve_batch_obs.argtypes = [C.POINTER(Config), C.c_int32, dp, dp, C.c_int32, dp, dp, dp, ip, ip, dp, C.c_int32]
+        _LIB.nmpc_oracle_solve_batch_obs.restype = C.c_int32
+        _LIB.nmpc_oracle_eval_batch_obs.argtypes = [C.POINTER(Config), C.c_int32, dp, dp, dp, C.c_int32, dp, dp]
+        _LIB.nmpc_oracle_eval_batch_obs.restype = C.c_int32
         _LIB.nmpc_oracle_shift_batch.argtypes = [C.POINTER(Config), C.c_int32, dp, dp, dp, dp]
         _LIB.nmpc_oracle_max_threads.restype = C.c_int32
         for f in ("nmpc_oracle_n_var", "nmpc_oracle_n_g", "nmpc_oracle_n_p"):
@@ -89,6 +93,45 @@ def eval_batch(cfg: Config, p: np.ndarray, w: np.ndarray):
     ng = L.nmpc_oracle_n_g(C.byref(cfg))
     f = np.empty(B); g = np.empty((B, ng))
     L.nmpc_oracle_eval_batch(C.byref(cfg), B, _dp(p), _dp(w), _dp(f), _dp(g))
+    return f, g
+
+
+def _field(cfg: Config, obs, B: int):
+    """a per-instance obstacle field [B, K, 3] (static) or [B, N, K, 3] (entry k at stage k) -> (contiguous [B, S, K, 3], S)"""
+    o = np.ascontiguousarray(obs, dtype=np.float64)
+    K, N = cfg.n_obs, cfg.N
+    if o.ndim == 3:
+        o = o.reshape(o.shape[0], 1, *o.shape[1:])
+    assert o.ndim == 4 and o.shape[0] == B and o.shape[1] in (1, N) and o.shape[2:] == (K, 3), (o.shape, B, N, K)
+    return np.ascontiguousarray(o), int(o.shape[1])
+
+
+def solve_batch_obs(cfg: Config, p: np.ndarray, obs, w0: np.ndarray, nthreads: int = 0):
+    """solve_batch with a per-instance obstacle field instead of cfg.obs (nmpc_oracle_solve_batch_obs; the rules of nmpc_solve_batch_obs)"""
+    L = lib()
+    p = np.ascontiguousarray(p, dtype=np.float64); w0 = np.ascontiguousarray(w0, dtype=np.float64)
+    B = p.shape[0]
+    nv = L.nmpc_oracle_n_var(C.byref(cfg))
+    assert p.shape == (B, 6 * cfg.m) and w0.shape == (B, nv)
+    o, S = _field(cfg, obs, B)
+    w = np.empty((B, nv)); obj = np.empty(B); kkt = np.empty(B)
+    st = np.empty(B, dtype=np.int32); it = np.empty(B, dtype=np.int32)
+    rc = L.nmpc_oracle_solve_batch_obs(C.byref(cfg), B, _dp(p), _dp(o), S, _dp(w0), _dp(w), _dp(obj),
+                                       st.ctypes.data_as(C.POINTER(C.c_int32)), it.ctypes.data_as(C.POINTER(C.c_int32)), _dp(kkt), nthreads)
+    assert rc == 0, rc
+    return dict(x=w, f=obj, status=st, iters=it, kkt=kkt)
+
+
+def eval_batch_obs(cfg: Config, p: np.ndarray, w: np.ndarray, obs):
+    """eval_batch with a per-instance obstacle field (nmpc_oracle_eval_batch_obs)"""
+    L = lib()
+    p = np.ascontiguousarray(p, dtype=np.float64); w = np.ascontiguousarray(w, dtype=np.float64)
+    B = p.shape[0]
+    o, S = _field(cfg, obs, B)
+    ng = L.nmpc_oracle_n_g(C.byref(cfg))
+    f = np.empty(B); g = np.empty((B, ng))
+    rc = L.nmpc_oracle_eval_batch_obs(C.byref(cfg), B, _dp(p), _dp(w), _dp(o), S, _dp(f), _dp(g))
+    assert rc == 0, rc
     return f, g
 
 

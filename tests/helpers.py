@@ -62,9 +62,10 @@ def bench_batch(name, B=0, rank=0, shard=None):
     return to_oracle_cfg(pcfg), B, P, W0
 
 
-def closed_loop_oracle(ocfg, x0, goals, max_steps, stop_tol=5e-2, max_iter=2000):
+def closed_loop_oracle(ocfg, x0, goals, max_steps, stop_tol=5e-2, max_iter=2000, obstacle_paths=None):
     """The reference's main loop (casadi_test.py:143-183; goal sequencing of centralized_one_robots_implementation.py:176-239)
-    driven by the CPU oracle — checker for nmpc_amd.simulate_closed_loop."""
+    driven by the CPU oracle — checker for nmpc_amd.simulate_closed_loop.  obstacle_paths [B, L, K, 3] (L >= max_steps + N): the solve of
+    period t sees rows t .. t+N-1 of its swarm's paths (oracle_lib.solve_batch_obs), as simulate_closed_loop(obstacle_paths=)."""
     from oracle import oracle_lib as O
     oc = O.make_config(ocfg, max_iter=max_iter)
     x = np.array(x0, dtype=np.float64); B, nx = x.shape
@@ -76,7 +77,7 @@ def closed_loop_oracle(ocfg, x0, goals, max_steps, stop_tol=5e-2, max_iter=2000)
     w = np.stack([R.cold_start(ocfg, xi) for xi in x])
     arrived = np.zeros(B, dtype=bool); arrival = np.full(B, -1)
     states = [x.copy()]
-    steps = 0
+    steps = failed = 0
     for step in range(max_steps):
         err = np.linalg.norm(x - g[ar, gi], axis=1)
         hit = (err <= stop_tol) & ~arrived
@@ -86,14 +87,18 @@ def closed_loop_oracle(ocfg, x0, goals, max_steps, stop_tol=5e-2, max_iter=2000)
         if arrived.all():
             break
         p = np.concatenate([x, g[ar, gi]], axis=1)
-        r = O.solve_batch(oc, p, w)
+        if obstacle_paths is None:
+            r = O.solve_batch(oc, p, w)
+        else:
+            r = O.solve_batch_obs(oc, p, np.asarray(obstacle_paths, dtype=np.float64)[:, step:step + ocfg.N], w)
+        failed += int((r["status"] != 0).sum())
         w, xn = O.shift_batch(oc, p, r["x"])
         x = np.where(arrived[:, None], x, xn)
         states.append(x.copy()); steps += 1
     err = np.linalg.norm(x - g[ar, gi], axis=1)
     late = (err <= stop_tol) & (gi == G - 1) & ~arrived
     arrival[late] = steps; arrived |= late
-    return dict(steps=steps, arrived=arrived, arrival_step=arrival, final_error=err, states=np.stack(states))
+    return dict(steps=steps, arrived=arrived, arrival_step=arrival, final_error=err, states=np.stack(states), failed_solves=failed)
 
 
 def to_oracle_cfg(pcfg):

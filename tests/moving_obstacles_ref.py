@@ -83,3 +83,42 @@ def obstacle_values(cfg, w, obs):
     o = field(cfg, obs)
     xy = X[: cfg.N].reshape(cfg.N, cfg.m, 3)[:, :, None, :2]
     return np.linalg.norm(xy - o[:, None, :, :2], axis=3) - cfg.rob_dim - o[:, None, :, 2]
+
+
+def team_cfg(m, N, K, **kw):
+    """a team of m robots with K obstacle rows (their values come from the field), at the literals of the scripts that have one: the third
+    scenario's for one robot (T = 0.2), C6's for 2..6 (T = 0.3), C10's beyond (T = 0.1)"""
+    base = dict(T=0.3, dmin=0.4, v_max=0.15, w_max=1.5) if m <= 6 else dict(T=0.1, dmin=0.3, v_max=0.22, w_max=2.84)
+    if m == 1:
+        base = dict(T=0.2, dmin=0.0, v_max=0.2, w_max=1.0, pad_rows=False)
+    base.update(kw)
+    return R.NLPConfig(m=m, N=N, obstacles=[(0.0, 0.0, 0.1)] * K, rob_dim=0.2, margin=0.1, **base)
+
+
+def moving_batch(cfg, B, seed, L=None):
+    """B instances of cfg (any m, K, N) among K obstacles of their own, crossing the workspace at constant velocity (speed <= v_max / 2) with
+    the radius growing by <= 50 % over the L rows of the field (L = N: a per-stage solve field; L > N: closed-loop paths, row t = period t);
+    starts clear of every obstacle's row 0 — at its largest radius — by more than the margin, goals likewise of its last row.
+    Returns P [B, 2 n_x], the cold starts W0 [B, n_var] and the fields [B, L, K, 3]."""
+    from tests import helpers as Hh
+    rng = np.random.default_rng(seed)
+    N, K, T = cfg.N, cfg.K, cfg.T
+    L = N if L is None else L
+    k = np.arange(L)[:, None]
+    P, F = [], []
+    for _ in range(B):
+        c0 = rng.uniform(-1.5, 1.5, (K, 2))
+        ang = rng.uniform(-np.pi, np.pi, K); spd = rng.uniform(0.2, 0.5, K) * cfg.v_max
+        vel = np.stack([np.cos(ang), np.sin(ang)], axis=1) * spd[:, None]
+        r0 = rng.uniform(0.1, 0.15, K); grow = rng.uniform(0.0, 0.5, K)
+        f = np.empty((L, K, 3))
+        f[:, :, :2] = c0[None] + (k * T)[:, :, None] * vel[None]
+        f[:, :, 2] = r0[None] * (1.0 + grow[None] * k / max(L - 1, 1))
+        clear = cfg.rob_dim + cfg.margin + 0.1
+        s = Hh.sample_points(rng, cfg.m, cfg.dmin + 0.1, obstacles=[(x, y, r) for x, y, r in zip(f[0, :, 0], f[0, :, 1], f[-1, :, 2])], clear=clear)
+        g = Hh.sample_points(rng, cfg.m, cfg.dmin + 0.1, obstacles=[(x, y, r) for x, y, r in f[-1]], clear=clear)
+        x0 = np.concatenate([s, rng.uniform(-np.pi, np.pi, (cfg.m, 1))], axis=1).reshape(-1)
+        xs = np.concatenate([g, rng.uniform(-np.pi, np.pi, (cfg.m, 1))], axis=1).reshape(-1)
+        P.append(np.concatenate([x0, xs])); F.append(f)
+    P = np.stack(P)
+    return P, np.stack([R.cold_start(cfg, p[: cfg.nx]) for p in P]), np.stack(F)

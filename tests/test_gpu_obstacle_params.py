@@ -130,38 +130,13 @@ def _moving_cfg(N=10):
     return c
 
 
-def _moving_batch(cfg, B, seed):
-    """six robots, four obstacles crossing the workspace at constant velocity (speed <= v_max / 2), radius growing by <= 50 % over the horizon;
-    starts clear of every obstacle's entry 0 — at its largest radius — by more than the margin (goals likewise of its last entry)"""
-    rng = np.random.default_rng(seed)
-    N, K, T = cfg.N, cfg.K, cfg.T
-    k = np.arange(N)[:, None]
-    P, F = [], []
-    for _ in range(B):
-        c0 = rng.uniform(-1.5, 1.5, (K, 2))
-        ang = rng.uniform(-np.pi, np.pi, K); spd = rng.uniform(0.2, 0.5, K) * cfg.v_max
-        vel = np.stack([np.cos(ang), np.sin(ang)], axis=1) * spd[:, None]
-        r0 = rng.uniform(0.1, 0.15, K); grow = rng.uniform(0.0, 0.5, K)
-        f = np.empty((N, K, 3))
-        f[:, :, :2] = c0[None] + (k * T)[:, :, None] * vel[None]
-        f[:, :, 2] = r0[None] * (1.0 + grow[None] * k / (N - 1))
-        clear = cfg.rob_dim + cfg.margin + 0.1
-        s = Hh.sample_points(rng, cfg.m, cfg.dmin + 0.1, obstacles=[(x, y, r) for x, y, r in zip(f[0, :, 0], f[0, :, 1], f[-1, :, 2])], clear=clear)
-        g = Hh.sample_points(rng, cfg.m, cfg.dmin + 0.1, obstacles=[(x, y, r) for x, y, r in f[-1]], clear=clear)
-        x0 = np.concatenate([s, rng.uniform(-np.pi, np.pi, (cfg.m, 1))], axis=1).reshape(-1)
-        xs = np.concatenate([g, rng.uniform(-np.pi, np.pi, (cfg.m, 1))], axis=1).reshape(-1)
-        P.append(np.concatenate([x0, xs])); F.append(f)
-    P = np.stack(P)
-    return P, np.stack([R.cold_start(cfg, p[: cfg.nx]) for p in P]), np.stack(F)
-
-
 def test_moving_obstacles_eval_matches_restatement(built):
     """g of eval_batch(obstacles=[B, N, K, 3]) at random w equals the numpy restatement (oracle rows, obstacle rows with stage-indexed
     centres) to 1e-12."""
     import torch
     cfg = _moving_cfg(10)
     B = 64
-    P, W0, F = _moving_batch(cfg, B, 5)
+    P, W0, F = MO.moving_batch(cfg, B, 5)
     rng = np.random.default_rng(6)
     W = W0 + rng.normal(0.0, 0.3, W0.shape)
     s = _solver(cfg, B)
@@ -180,7 +155,7 @@ def test_moving_obstacles_solve_kkt(built):
     import torch
     cfg = _moving_cfg(10)
     B = 512
-    P, W0, F = _moving_batch(cfg, B, 7)
+    P, W0, F = MO.moving_batch(cfg, B, 7)
     r = _np(_solver(cfg, B, max_iter=2000).solve_batch(P, W0, obstacles=F)); torch.cuda.synchronize()
     ok = r["status"] == 0
     print(f"moving obstacles: status 0 on {ok.mean():.4f} of {B}, statuses {np.unique(r['status'], return_counts=True)}, mean iterations {r['iters'].mean():.2f}")
