@@ -22,6 +22,20 @@ int32_t nmpc_debug_trace2(nmpc_handle_t *h, double *out, int32_t rows);
    offs [5] (may be NULL) <- kernel, oKG, oKFF, oPACK, oKT */
 int64_t nmpc_debug_workspace(nmpc_handle_t *h, int32_t inst, double *out, int64_t cap, int64_t *offs);
 
+
+/* the kernel instantiation of one solve launch, as in its mangled name: solve_kernelILi{m}ELi{threads}E (kernel 1),
+   solve_lds_kernelILi{m}ELi{thb}ELi{threads}E (2), solve_col_kernelILi{m}ELi{thb}ELi{flags}ELi{threads}E (3) */
+typedef struct nmpc_debug_variant {
+    int32_t kernel;        /* 1 HBM-resident, 2 element-per-lane, 3 column-per-lane */
+    int32_t m, thb;        /* template team size, heading-bound flag (0 for kernel 1, which has no such template argument) */
+    int32_t flags;         /* column kernel: the DL template argument exactly as instantiated (0/1/2, | 4 with the per-instance field); else 0 */
+    int32_t threads;       /* workgroup size = TPB template argument */
+    int64_t lds_bytes;     /* dynamic LDS of the launch */
+} nmpc_debug_variant_t;
+/* the instantiation a solve of B instances on this handle would launch (ordered != 0: with a dispatch-order hint; obs_field != 0: an *_obs call).
+   No launch is made.  Returns NMPC_OK, NMPC_E_ARG, or NMPC_E_UNSUPPORTED where the call itself would. */
+int32_t nmpc_debug_variant(const nmpc_handle_t *h, int32_t B, int32_t ordered, int32_t obs_field, nmpc_debug_variant_t *out);
+
 #ifdef __cplusplus
 }
 #endif

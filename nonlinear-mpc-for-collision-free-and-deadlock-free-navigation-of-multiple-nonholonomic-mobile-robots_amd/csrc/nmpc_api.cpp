@@ -228,6 +228,18 @@ static int lat_waves_shape(const nmpc_handle_t *h, int32_t B)
     return (h->cfg.m >= 5 && h->cfg.m <= 6 && items > 1000 && B <= 2 * h->lat_slots4) ? 2 : 1;
 }
 
+// The launch a solve of B instances makes: kern as kernel_for_batch*() (4: the column kernel's latency shape), shape as launch_solve_col*
+// take it, and the instantiation the launcher of that kernel selects.  solve_impl() launches by it, nmpc_debug_variant() reports it.
+static bool launch_choice(const nmpc_handle_t *h, int32_t B, bool ordered, bool obs, int *kern, int *shape, nmpc::SolveVariant *v)
+{
+    *kern = obs ? kernel_for_batch_obs(h, B, ordered) : kernel_for_batch(h, B, ordered);
+    *shape = *kern == 4 ? lat_waves_shape(h, B) : 0;
+    if (obs) return nmpc::select_solve_col(h->P, h->cfg.m, *shape, true, v);
+    return *kern == 1   ? nmpc::select_solve(h->P, h->cfg.m, B, v)
+           : *kern == 2 ? nmpc::select_solve_lds(h->P, h->cfg.m, B, v)
+                        : nmpc::select_solve_col(h->P, h->cfg.m, *shape, false, v);
+}
+
 // the per-instance obstacle field of the *_obs entry points: NMPC_OK, or the error of a bad field (obs may be NULL only for an empty batch)
 static int32_t obs_field_check(const nmpc_handle_t *h, int32_t B, const double *obs, int32_t obs_stages)
 {
@@ -262,14 +274,16 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
     // faster.  Measured (solves/s, column | element), six robots: B=256 14.7 k | 16.7 k, 512 28.6 k | 31.0 k, 1024 54.0 k | 46.4 k,
     // 2048 97 k | 89 k, 4096 164 k | 104 k, 8192 205 k | 131 k, 16384 251 k | 145 k; ten robots N=20: B=256 10.4 k | 11.9 k,
     // 512 13.1 k | 13.4 k, 1024 25.5 k | 23.0 k, 2048 41.5 k | 25.5 k, 4096 59 k | 27 k; N=30: B=256 3.4 k | 3.8 k, 512 5.7 k | 4.7 k.
-    const int kern = obs ? kernel_for_batch_obs(h, B, order != nullptr) : kernel_for_batch(h, B, order != nullptr);
+    int kern, shape;
+    nmpc::SolveVariant var;
+    if (!launch_choice(h, B, order != nullptr, obs != nullptr, &kern, &shape, &var)) return NMPC_E_HIP;
     if (obs) {
-        hipError_t e = nmpc::launch_solve_col_obs(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, kern == 4 ? lat_waves_shape(h, B) : 0);
+        hipError_t e = nmpc::launch_solve_col_obs(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, shape);
         return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
     }
     hipError_t e = (kern == 1)   ? nmpc::launch_solve(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, (hipStream_t)stream)
                    : (kern == 2) ? nmpc::launch_solve_lds(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream)
-                                 : nmpc::launch_solve_col(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, kern == 4 ? lat_waves_shape(h, B) : 0);
+                                 : nmpc::launch_solve_col(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, shape);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 
@@ -439,6 +453,19 @@ int64_t nmpc_debug_workspace(nmpc_handle_t *h, int32_t inst, double *out, int64_
     if (hipDeviceSynchronize() != hipSuccess) return NMPC_E_HIP;
     if (hipMemcpy(out, h->ws + (size_t)inst * per, (size_t)per * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return NMPC_E_HIP;
     return per;
+}
+
+/* the instantiation a solve of B instances on this handle would launch; no launch is made */
+int32_t nmpc_debug_variant(const nmpc_handle_t *h, int32_t B, int32_t ordered, int32_t obs_field, nmpc_debug_variant_t *out)
+{
+    if (!h || !out || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    if (obs_field && h->cfg.n_obs == 0) return NMPC_E_ARG;      // as obs_field_check()
+    if (obs_field && h->kernel != 3) return NMPC_E_UNSUPPORTED;
+    int kern, shape;
+    nmpc::SolveVariant v;
+    if (!launch_choice(h, B, ordered != 0, obs_field != 0, &kern, &shape, &v)) return NMPC_E_UNSUPPORTED;
+    out->kernel = v.kernel; out->m = v.m; out->thb = v.thb; out->flags = v.flags; out->threads = v.threads; out->lds_bytes = (int64_t)v.lds;
+    return NMPC_OK;
 }
 
 #ifndef NMPC_SRC_HASH

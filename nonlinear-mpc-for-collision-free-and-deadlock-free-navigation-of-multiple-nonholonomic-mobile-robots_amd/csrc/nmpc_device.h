@@ -38,6 +38,17 @@ struct KParams {
     int32_t oX, oU, oLAM, oS, oZ, oDX, oDU, oLAMN, oDS, oDZ, oSN, oCS, oC, oH, oGX, oHUU, oGU, oHVT, oHTT, oKG, oKFF, oCKP, oEL;      // oCKP: the HBM-resident kernel's saved cost-to-go, [(N-1)/NMPC_CKPT_EVERY + 1][nx * nx + nx]; oEL: its elastic variables, one per inequality slot
 };
 
+// The instantiation one launch runs: the template arguments of solve_kernel<M, TPB> (kernel 1), solve_lds_kernel<M, THB, TPB> (2) or
+// solve_col_kernel<M, THB, DL, TPB> (3), and its dynamic LDS.  Filled by the select_* function of each kernel, which its launcher calls too.
+struct SolveVariant {
+    int kernel, m, thb, flags, threads;      // thb: 0 for kernel 1 (no such template argument); flags: DL of the column kernel, else 0
+    size_t lds;
+};
+// false: team size not instantiated
+bool select_solve(const KParams &P, int m, int B, SolveVariant *v);
+bool select_solve_lds(const KParams &P, int m, int B, SolveVariant *v);
+bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVariant *v);      // shape and ofield as launch_solve_col / launch_solve_col_obs
+
 hipError_t launch_solve(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
                         int32_t *iters, double *kkt, double *ws, hipStream_t st);
 hipError_t launch_solve_lds(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,

@@ -976,10 +976,12 @@ __global__ __launch_bounds__(256) void shift_kernel(const KParams P, int B, cons
 
 // ------------------------------------------------------------------------------------------
 // host-side launchers (called from nmpc_api.cpp)
+// workgroup size of the HBM-resident kernel: its only choice (no dynamic LDS, no heading-bound template argument)
+template <int M_> static constexpr int solve_threads() { return (M_ <= 6) ? 64 : 128; }
 template <int M_> static hipError_t launch_solve_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
                                                    int32_t *status, int32_t *iters, double *kkt, double *ws, hipStream_t st)
 {
-    constexpr int TPB = (M_ <= 6) ? 64 : 128;
+    constexpr int TPB = solve_threads<M_>();
     hipLaunchKernelGGL((solve_kernel<M_, TPB>), dim3(B), dim3(TPB), 0, st, P, p, w0, w_out, obj, status, iters, kkt, ws);
     return hipGetLastError();
 }
@@ -1103,6 +1105,16 @@ hipError_t launch_solve(const KParams &P, int m, int B, const double *p, const d
 {
 #define C_(M) launch_solve_m<M>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, st)
     NMPC_DISPATCH(m, C_)
+#undef C_
+}
+bool select_solve(const KParams &, int m, int, SolveVariant *v)
+{
+#define C_(M) (*v = SolveVariant{1, M, 0, 0, solve_threads<M>(), 0}, true)
+    switch (m) {
+    case 1: return C_(1); case 2: return C_(2); case 3: return C_(3); case 4: return C_(4); case 5: return C_(5);
+    case 6: return C_(6); case 7: return C_(7); case 8: return C_(8); case 9: return C_(9); case 10: return C_(10);
+    default: return false;
+    }
 #undef C_
 }
 hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)

@@ -1680,32 +1680,50 @@ template <int M_, int THB> static int col_factor_mode(const KParams &P)
 }
 
 // OBS = 1: the instantiations of the per-instance obstacle field (P.ofield), in the same shapes and data layouts as the plain ones
+template <int M_, int OBS> struct ColInst {
+    static constexpr int OB = OBS ? NMPC_DL_OBS : 0;
+    static constexpr int DLmax = (M_ <= NMPC_COL_DL_MAXM) ? 1 : 0;
+    // latency shape (two wavefronts per instance): slacks and duals in LDS up to six robots — occupancy is not what a launch that lasts as
+    // long as its longest solve is short of — and in the workspace for eight and ten
+    static constexpr int DLlat = (M_ <= 6) ? 1 : 0;
+    static constexpr int FLM = (M_ >= NMPC_COL_FL_MINM && M_ <= NMPC_COL_FL_MAXM) ? NMPC_COL_FL_MODE : 1;      // instantiated only for the team sizes of the switch
+    // four wavefronts per instance (shape 2) are instantiated for five and six robots only: they pay where a phase has > 1000 items (eight
+    // obstacles: composite B=1024 28.7 k -> 33.5 k solves/s; six robots without obstacles B=512 42.3 k -> 43.4 k) and the build time counts
+    static constexpr int TPB4 = (M_ == 5 || M_ == 6) ? 256 : 128;
+};
+// the instantiation a launch in the given shape runs (shape: 0 throughput, 1 / 2 latency with two / four wavefronts per instance)
+template <int M_, int THB, int OBS> static SolveVariant select3_mt(const KParams &P, int shape)
+{
+    using I = ColInst<M_, OBS>;
+    const bool lat = shape >= 1;
+    const bool dl = lat ? (I::DLlat != 0) : (I::DLmax && col_duals_in_lds<M_, THB>(P));
+    const int fl = (!lat && dl) ? col_factor_mode<M_, THB>(P) : 0;
+    const size_t lds = col_lds_bytes<M_, THB>(P, dl, fl);
+    if (shape == 2 && I::TPB4 == 128) shape = 1;
+    if (shape == 2) return SolveVariant{3, M_, THB, I::DLlat | I::OB, I::TPB4, lds};
+    if (lat) return SolveVariant{3, M_, THB, I::DLlat | I::OB, 128, lds};
+    if (fl) return SolveVariant{3, M_, THB, I::DLmax * I::FLM | I::OB, 64, lds};
+    return SolveVariant{3, M_, THB, (dl ? I::DLmax : 0) | I::OB, 64, lds};
+}
 template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
                                                         int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape)
 {
-    constexpr int OB = OBS ? NMPC_DL_OBS : 0;
-    constexpr int DLmax = (M_ <= NMPC_COL_DL_MAXM) ? 1 : 0;
-    // latency shape (two wavefronts per instance): slacks and duals in LDS up to six robots — occupancy is not what a launch that lasts as
-    // long as its longest solve is short of — and in the workspace for eight and ten
-    constexpr int DLlat = (M_ <= 6) ? 1 : 0;
-    const bool lat = shape >= 1;
-    const bool dl = lat ? (DLlat != 0) : (DLmax && col_duals_in_lds<M_, THB>(P));
-    constexpr int FLM = (M_ >= NMPC_COL_FL_MINM && M_ <= NMPC_COL_FL_MAXM) ? NMPC_COL_FL_MODE : 1;      // instantiated only for the team sizes of the switch
-    const int fl = (!lat && dl) ? col_factor_mode<M_, THB>(P) : 0;
-    size_t lds = col_lds_bytes<M_, THB>(P, dl, fl);
+    using I = ColInst<M_, OBS>;
+    const SolveVariant v = select3_mt<M_, THB, OBS>(P, shape);
+    const size_t lds = v.lds;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    // four wavefronts per instance (shape 2) are instantiated for five and six robots only: they pay where a phase has > 1000 items (eight
-    // obstacles: composite B=1024 28.7 k -> 33.5 k solves/s; six robots without obstacles B=512 42.3 k -> 43.4 k) and the build time counts
-    constexpr int TPB4 = (M_ == 5 || M_ == 6) ? 256 : 128;
-    if (shape == 2 && TPB4 == 128) shape = 1;
-    auto kern = shape == 2 ? solve_col_kernel<M_, THB, DLlat | OB, TPB4>
-                           : (lat ? solve_col_kernel<M_, THB, DLlat | OB, 128>
-                                  : (fl ? solve_col_kernel<M_, THB, DLmax * FLM | OB, 64> : (dl ? solve_col_kernel<M_, THB, DLmax | OB, 64> : solve_col_kernel<M_, THB, OB, 64>)));
+    // the instantiation whose template arguments are v's
+    auto kern = (v.threads == I::TPB4 && v.flags == (I::DLlat | I::OB)) ? solve_col_kernel<M_, THB, I::DLlat | I::OB, I::TPB4>
+                : (v.threads == 128 && v.flags == (I::DLlat | I::OB)) ? solve_col_kernel<M_, THB, I::DLlat | I::OB, 128>
+                : (v.threads == 64 && v.flags == (I::DLmax * I::FLM | I::OB)) ? solve_col_kernel<M_, THB, I::DLmax * I::FLM | I::OB, 64>
+                : (v.threads == 64 && v.flags == (I::DLmax | I::OB)) ? solve_col_kernel<M_, THB, I::DLmax | I::OB, 64>
+                : (v.threads == 64 && v.flags == I::OB) ? solve_col_kernel<M_, THB, I::OB, 64> : nullptr;
+    if (!kern) return hipErrorInvalidValue;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(shape == 2 ? 256 : (lat ? 128 : 64)), lds, st, P, p, w0, w_out, obj, status, iters, kkt, ws, prof);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(v.threads), lds, st, P, p, w0, w_out, obj, status, iters, kkt, ws, prof);
     return hipGetLastError();
 }
 template <int M_, int OBS> static hipError_t launch3_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
@@ -1806,6 +1824,17 @@ hipError_t launch_solve_col_obs(COL_ARGS_DECL)
 #endif
     default: return hipErrorInvalidValue;
     }
+}
+
+bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVariant *v)
+{
+#define C_(M) (*v = ofield ? (P.thb ? select3_mt<M, 1, 1>(P, shape) : select3_mt<M, 0, 1>(P, shape)) : (P.thb ? select3_mt<M, 1, 0>(P, shape) : select3_mt<M, 0, 0>(P, shape)), true)
+    switch (m) {
+    case 1: return C_(1); case 2: return C_(2); case 3: return C_(3); case 4: return C_(4); case 5: return C_(5);
+    case 6: return C_(6); case 7: return C_(7); case 8: return C_(8); case 9: return C_(9); case 10: return C_(10);
+    default: return false;
+    }
+#undef C_
 }
 
 // LDS bytes one instance of the column-per-lane kernel needs in the given shape (0 if m is not supported)

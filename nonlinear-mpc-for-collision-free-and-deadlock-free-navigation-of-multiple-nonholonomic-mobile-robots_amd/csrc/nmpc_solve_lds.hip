@@ -1170,8 +1170,10 @@ template <int M_, int THB, int TPB> static hipError_t launch2_mtt(const KParams 
     return hipGetLastError();
 }
 
-template <int M_, int THB> static hipError_t launch2_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
-                                                        int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st)
+// workgroup size of the throughput shape
+template <int M_> static constexpr int lds_tp_threads() { return (M_ <= 6) ? 64 : (M_ <= 8 ? 128 : 256); }
+// workgroup size of one launch of B instances
+template <int M_, int THB> static int lds_threads(const KParams &P, int B)
 {
     // Throughput shape: one wave per instance up to six robots (4 instances per CU, 1024 resident on the chip); the augmented
     // matrix of 8 / 10 robots (860 / 1325 elements) is spread over 2 / 4 waves so that the per-thread element tables stay in
@@ -1182,10 +1184,27 @@ template <int M_, int THB> static hipError_t launch2_mt(const KParams &P, int B,
     // (the wider shapes carry a larger 16-bit element table: a horizon that only fits the 160 KB of LDS in the throughput
     // shape stays on it)
     if constexpr (M_ == 5 || M_ == 6) {
-        if (B <= 256 && lds_bytes<M_, THB>(P, 256) <= (size_t)160 * 1024) return launch2_mtt<M_, THB, 256>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-        if (B <= 512 && lds_bytes<M_, THB>(P, 128) <= (size_t)160 * 1024) return launch2_mtt<M_, THB, 128>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
+        if (B <= 256 && lds_bytes<M_, THB>(P, 256) <= (size_t)160 * 1024) return 256;
+        if (B <= 512 && lds_bytes<M_, THB>(P, 128) <= (size_t)160 * 1024) return 128;
     }
-    constexpr int TPB = (M_ <= 6) ? 64 : (M_ <= 8 ? 128 : 256);
+    return lds_tp_threads<M_>();
+}
+template <int M_, int THB> static SolveVariant select2_mt(const KParams &P, int B)
+{
+    const int tpb = lds_threads<M_, THB>(P, B);
+    return SolveVariant{2, M_, THB, 0, tpb, lds_bytes<M_, THB>(P, tpb)};
+}
+
+template <int M_, int THB> static hipError_t launch2_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
+                                                        int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st)
+{
+    const int tpb = select2_mt<M_, THB>(P, B).threads;
+    if constexpr (M_ == 5 || M_ == 6) {
+        if (tpb == 256) return launch2_mtt<M_, THB, 256>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
+        if (tpb == 128) return launch2_mtt<M_, THB, 128>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
+    }
+    constexpr int TPB = lds_tp_threads<M_>();
+    if (tpb != TPB) return hipErrorInvalidValue;
     return launch2_mtt<M_, THB, TPB>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
 }
 template <int M_> static hipError_t launch2_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
@@ -1213,13 +1232,24 @@ hipError_t launch_solve_lds(const KParams &P, int m, int B, const double *p, con
     }
 }
 
+bool select_solve_lds(const KParams &P, int m, int B, SolveVariant *v)
+{
+#define C_(M) (*v = P.thb ? select2_mt<M, 1>(P, B) : select2_mt<M, 0>(P, B), true)
+    switch (m) {
+    case 1: return C_(1); case 2: return C_(2); case 3: return C_(3); case 4: return C_(4); case 5: return C_(5);
+    case 6: return C_(6); case 7: return C_(7); case 8: return C_(8); case 9: return C_(9); case 10: return C_(10);
+    default: return false;
+    }
+#undef C_
+}
+
 // LDS bytes one instance of the LDS-resident kernel needs in its throughput shape (0 if m is not supported); the C ABI falls
 // back to the HBM-resident kernel when this exceeds the 160 KB of a CU
 size_t lds_kernel_bytes(const KParams &P, int m)
 {
-#define LB(M, T) case M: return P.thb ? lds_bytes<M, 1>(P, T) : lds_bytes<M, 0>(P, T);
+#define LB(M) case M: return P.thb ? lds_bytes<M, 1>(P, lds_tp_threads<M>()) : lds_bytes<M, 0>(P, lds_tp_threads<M>());
     switch (m) {
-        LB(1, 64) LB(2, 64) LB(3, 64) LB(4, 64) LB(5, 64) LB(6, 64) LB(7, 128) LB(8, 128) LB(9, 256) LB(10, 256)
+        LB(1) LB(2) LB(3) LB(4) LB(5) LB(6) LB(7) LB(8) LB(9) LB(10)
     default: return 0;
     }
 #undef LB

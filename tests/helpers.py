@@ -1,5 +1,10 @@
 """Synthetic instance generator of SURVEY.md §8(d): PCG64(seed = 20210141 + config_index)."""
+import os
+import re
+import subprocess
+
 import numpy as np
+import pytest
 
 from oracle import nlp_ref as R
 
@@ -178,3 +183,33 @@ def lidar_episode_batch(seed, B):
                 obs.append((c[0], c[1], rng.uniform(0.06, 0.1)))
         world.append(np.array(obs)); pose0.append(p0); goals.append(np.stack([g1, g2]))
     return np.stack(pose0), np.stack(goals), np.stack(world)
+
+
+def kernel_notes(tmp_path):
+    """{kernel symbol: {vgpr_count, private_segment_fixed_size}} of every kernel in the gfx950 code objects of lib/libnmpc_hip.so"""
+    import importlib
+    bld = importlib.import_module("nmpc_amd.build")
+    tools = "/opt/rocm/lib/llvm/bin"
+    if not (os.path.exists(os.path.join(tools, "llvm-objcopy")) and os.path.exists(os.path.join(tools, "llvm-readelf"))):
+        pytest.skip("no llvm-objcopy / llvm-readelf")
+    fat = str(tmp_path / "fat.bin")
+    subprocess.check_call([os.path.join(tools, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, bld.SO, str(tmp_path / "copy.so")])
+    data = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(b"\x7fELF", data)]
+    res = {}
+    for n, a in enumerate(starts):
+        p = str(tmp_path / ("co%d.elf" % n))
+        with open(p, "wb") as f:
+            f.write(data[a:starts[n + 1] if n + 1 < len(starts) else len(data)])
+        notes = subprocess.run([os.path.join(tools, "llvm-readelf"), "--notes", p], capture_output=True, text=True).stdout
+        for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+            name = re.search(r"\n\s+\.name:\s+(\S+)", blk)
+            if not name:
+                continue
+            d = {}
+            for key in ("vgpr_count", "private_segment_fixed_size"):
+                m = re.search(r"\n\s+\.%s:\s+(\d+)" % key, blk)
+                if m:
+                    d[key] = int(m.group(1))
+            res[name.group(1)] = d
+    return res

@@ -30,41 +30,11 @@ def test_obstacle_entry_points_declared_and_exported(built):
         assert len(getattr(L, n).argtypes) == {"nmpc_eval_batch_obs": 9}.get(n, 13), n
 
 
-def _kernel_notes(tmp_path):
-    """{kernel symbol: {vgpr_count, private_segment_fixed_size}} of every kernel in the gfx950 code objects of lib/libnmpc_hip.so"""
-    import importlib
-    bld = importlib.import_module("nmpc_amd.build")
-    tools = "/opt/rocm/lib/llvm/bin"
-    if not (os.path.exists(os.path.join(tools, "llvm-objcopy")) and os.path.exists(os.path.join(tools, "llvm-readelf"))):
-        pytest.skip("no llvm-objcopy / llvm-readelf")
-    fat = str(tmp_path / "fat.bin")
-    subprocess.check_call([os.path.join(tools, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, bld.SO, str(tmp_path / "copy.so")])
-    data = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(b"\x7fELF", data)]
-    res = {}
-    for n, a in enumerate(starts):
-        p = str(tmp_path / ("co%d.elf" % n))
-        with open(p, "wb") as f:
-            f.write(data[a:starts[n + 1] if n + 1 < len(starts) else len(data)])
-        notes = subprocess.run([os.path.join(tools, "llvm-readelf"), "--notes", p], capture_output=True, text=True).stdout
-        for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-            name = re.search(r"\n\s+\.name:\s+(\S+)", blk)
-            if not name:
-                continue
-            d = {}
-            for key in ("vgpr_count", "private_segment_fixed_size"):
-                m = re.search(r"\n\s+\.%s:\s+(\d+)" % key, blk)
-                if m:
-                    d[key] = int(m.group(1))
-            res[name.group(1)] = d
-    return res
-
-
 def test_fatbin_holds_the_obstacle_field_instantiations(built, tmp_path):
     """The per-instance field instantiations of the column kernel (bit 2 of DL: DL = 4..7) exist for every team size in every shape the plain
     ones have, under the solve_col_kernel name the build checks select; up to six robots they stay within 256 VGPRs in the throughput shape and
     within the plain ones' scratch limit, the six-robot ones without scratch; the eval kernel has one per team size (team size + 16)."""
-    notes = _kernel_notes(tmp_path)
+    notes = Hh.kernel_notes(tmp_path)
     col = {}
     for k, v in notes.items():
         m = re.search(r"solve_col_kernelILi(\d+)ELi(\d)ELi(\d)ELi(\d+)E", k)
