@@ -217,6 +217,56 @@ int32_t nmpc_eval_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const 
                             void *stream);
 
 /*
+ * The solver's own multipliers: sol['lam_g'], sol['lam_x'], sol['lam_p'] of the CasADi call (C6:432), and a KKT certificate of any
+ * (w, lam_g, lam_x) for a whole batch on the device.
+ *
+ * Convention (CasADi's): L = f + lam_g' g + lam_x' w + lam_p' p with grad_w L = 0 and grad_p L = 0 at a solution; a multiplier is <= 0 on an
+ * active lower bound and >= 0 on an active upper bound.  The layouts are those of g, w and p everywhere else in this header (the row order
+ * of nmpc_eval_batch).
+ *   lam_g [B][n_g]   defect rows of stage k (g = X_{k+1} - F(X_k, U_k)): the solver's multiplier of that defect, with the sign of that g;
+ *                    pair and obstacle rows of stages 1..N-1: minus the solver's dual z >= 0 (the rows are bounded below, so the value is <= 0);
+ *                    pad rows: 0;
+ *                    pair and obstacle rows of stage 0: 0 BY DEFINITION — they act on the pinned X_0, the solver gives them no slack, and the
+ *                    constraint qualification fails there;
+ *                    initial block X_0 - x0: from stationarity in X_0, -(2 Q (X_0 - xs) + (d c_0 / d X_0)' lam_g[c_0]) with c_0 the defect of
+ *                    stage 0 — it absorbs whatever the stage-0 rows would carry.
+ *   lam_x [B][n_var] controls: (dual of the upper bound) - (dual of the lower bound); bounded components of X_1..X_N: the same; X_0: 0;
+ *                    headings when th_max = +inf: 0.
+ *   lam_p [B][n_p]   the x0 part equals lam_g[:n_x] (bit for bit); the xs part is 2 Q sum_{k<N} (X_k - xs).  Both follow from grad_p L = 0, so
+ *                    d f* / d p = -lam_p: the sensitivity of the optimal cost to the measured state and to the goal.
+ * By status: 0 (including a solve that converged in the elastic phase with its elastic variables closed): the multipliers of the returned
+ * point, for which the solve's own optimality test held; 1 / 4: those of the last iterate; 2: whatever the iterate holds, possibly non-finite;
+ * 3 (the return before the iteration): all three rows are zero.
+ *
+ * nmpc_solve_batch_duals / nmpc_step_batch_duals are nmpc_solve_batch_ordered / nmpc_step_batch (obs == NULL and obs_stages == 0: the
+ * handle's own obstacle field) or nmpc_solve_batch_obs / nmpc_step_batch_obs (otherwise, by their rules) that also write the multipliers;
+ * order may be NULL.  Each member of *duals is a device pointer or NULL (not written); duals == NULL, or all three members NULL, is exactly
+ * the call without multipliers, and w_out, obj, status, iters, kkt never depend on them.  The step call returns the multipliers of this
+ * period's w_sol.  The multipliers are written by the column-per-lane kernel (every shape): where the plain call would run the
+ * element-per-lane kernel these run the column kernel's throughput shape, and handles that run on kernel 1 or 2 get NMPC_E_UNSUPPORTED from
+ * both calls (as from the *_obs calls).
+ *
+ * nmpc_kkt_batch evaluates, for given w [B][n_var], lam_g [B][n_g], lam_x [B][n_var] (any: a solve's output or a caller's own),
+ *   grad_lag [B][n_var] = grad f + J' lam_g + lam_x   (written when not NULL; the stage-0 rows enter with the multipliers given) and
+ *   res [B][6] = (stat, eq, ineq, bnd, compl, sign):
+ *     stat   inf-norm of grad_lag
+ *     eq     largest |g_i| over the equality rows (initial block, defects)
+ *     ineq   largest violation lbg_i - g_i of an inequality row (pad, pair, obstacle), at least 0
+ *     bnd    largest violation of a variable bound, at least 0
+ *     compl  largest of |lam_g_i| (g_i - lbg_i) over the inequality rows and of max(-lam_x_j, 0) (w_j - lbx_j), max(lam_x_j, 0) (ubx_j - w_j)
+ *            over the finite variable bounds, at least 0
+ *     sign   largest positive lam_g_i on an inequality row (all are bounded below), at least 0
+ *   A NaN in the inputs reaches the numbers it enters.  (obs, obs_stages) as above.  Works on every handle, like nmpc_eval_batch.
+ */
+typedef struct nmpc_duals { double *lam_g, *lam_x, *lam_p; } nmpc_duals_t;   /* device, each may be NULL */
+int32_t nmpc_solve_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
+                               double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order, const nmpc_duals_t *duals, void *stream);
+int32_t nmpc_step_batch_duals(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *obs, int32_t obs_stages, double *obj,
+                              int32_t *status, int32_t *iters, double *kkt, int32_t *order, const nmpc_duals_t *duals, void *stream);
+int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                       const double *lam_x, double *res /* [B][6] */, double *grad_lag /* [B][n_var] or NULL */, void *stream);
+
+/*
  * Odometry front-end of the scripts' callbacks (AS/centralized_two_robots_implementation.py:18-37): for n robots,
  *   odom [n][4] = (x_r, y_r, q_z, q_w) wheel-odometry pose in the robot's own start frame (q_w is carried but, as in the
  *                  reference, not used: yaw = 2 asin(q_z)),

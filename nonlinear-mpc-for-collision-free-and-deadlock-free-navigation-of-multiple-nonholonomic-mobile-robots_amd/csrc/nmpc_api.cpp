@@ -230,9 +230,10 @@ static int lat_waves_shape(const nmpc_handle_t *h, int32_t B)
 
 // The launch a solve of B instances makes: kern as kernel_for_batch*() (4: the column kernel's latency shape), shape as launch_solve_col*
 // take it, and the instantiation the launcher of that kernel selects.  solve_impl() launches by it, nmpc_debug_variant() reports it.
-static bool launch_choice(const nmpc_handle_t *h, int32_t B, bool ordered, bool obs, int *kern, int *shape, nmpc::SolveVariant *v)
+// col: the call needs the column kernel (an obstacle field, or the multipliers: h->kernel == 3 is the caller's check)
+static bool launch_choice(const nmpc_handle_t *h, int32_t B, bool ordered, bool obs, int *kern, int *shape, nmpc::SolveVariant *v, bool col = false)
 {
-    *kern = obs ? kernel_for_batch_obs(h, B, ordered) : kernel_for_batch(h, B, ordered);
+    *kern = (obs || col) ? kernel_for_batch_obs(h, B, ordered) : kernel_for_batch(h, B, ordered);
     *shape = *kern == 4 ? lat_waves_shape(h, B) : 0;
     if (obs) return nmpc::select_solve_col(h->P, h->cfg.m, *shape, true, v);
     return *kern == 1   ? nmpc::select_solve(h->P, h->cfg.m, B, v)
@@ -248,13 +249,18 @@ static int32_t obs_field_check(const nmpc_handle_t *h, int32_t B, const double *
     return NMPC_OK;
 }
 
+static bool wants_duals(const nmpc_duals_t *d) { return d && (d->lam_g || d->lam_x || d->lam_p); }
+
 // obs != NULL: the obstacle field of the instances, [B][obs_stages][n_obs][3] (checked by obs_field_check), read by the column kernel's
-// per-instance field instantiations; handles that run on kernel 1 or 2 have none
+// per-instance field instantiations; handles that run on kernel 1 or 2 have none.  duals: the multiplier outputs of the *_duals entry points,
+// written by the column kernel's epilogue (nullptr, or all members nullptr: the plain call)
 static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                          int32_t *iters, double *kkt, const int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0)
+                          int32_t *iters, double *kkt, const int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0,
+                          const nmpc_duals_t *duals = nullptr)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    if (obs && h->kernel != 3) return NMPC_E_UNSUPPORTED;      // horizon beyond the column kernel's LDS, or a pin to kernel 1 / 2
+    const bool du = wants_duals(duals);
+    if ((obs || du) && h->kernel != 3) return NMPC_E_UNSUPPORTED;      // horizon beyond the column kernel's LDS, or a pin to kernel 1 / 2
     if (B == 0) return NMPC_OK;      /* empty batch: nothing to read or write, pointers may be null */
     if (!p || !w0 || !w_out) return NMPC_E_ARG;
     DeviceScope dev(h->device);
@@ -267,6 +273,7 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
         P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
         P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
     }
+    if (du) { P.lam_g = duals->lam_g; P.lam_x = duals->lam_x; P.lam_p = duals->lam_p; }
     if (order && nmpc::launch_order_check(B, order, h->ord_chk, h->ord_chk + B, (hipStream_t)stream) != hipSuccess) return NMPC_E_HIP;
     // Launch shape.  The column-per-lane kernel (one wave per instance, two instances per SIMD up to six robots) is the
     // throughput path.  A batch that cannot fill those slots is a latency problem instead (the launch lasts as long as its longest
@@ -276,7 +283,7 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
     // 512 13.1 k | 13.4 k, 1024 25.5 k | 23.0 k, 2048 41.5 k | 25.5 k, 4096 59 k | 27 k; N=30: B=256 3.4 k | 3.8 k, 512 5.7 k | 4.7 k.
     int kern, shape;
     nmpc::SolveVariant var;
-    if (!launch_choice(h, B, order != nullptr, obs != nullptr, &kern, &shape, &var)) return NMPC_E_HIP;
+    if (!launch_choice(h, B, order != nullptr, obs != nullptr, &kern, &shape, &var, du)) return NMPC_E_HIP;
     if (obs) {
         hipError_t e = nmpc::launch_solve_col_obs(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, shape);
         return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
@@ -300,16 +307,16 @@ int32_t nmpc_solve_batch_ordered(nmpc_handle_t *h, int32_t B, const double *p, c
 }
 
 static int32_t step_impl(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, double *obj, int32_t *status, int32_t *iters, double *kkt,
-                         int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0)
+                         int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0, const nmpc_duals_t *duals = nullptr)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    if (obs && h->kernel != 3) return NMPC_E_UNSUPPORTED;
+    if ((obs || wants_duals(duals)) && h->kernel != 3) return NMPC_E_UNSUPPORTED;
     if (B == 0) return NMPC_OK;
     if (!p || !w || !w_sol || w == w_sol) return NMPC_E_ARG;
     int32_t *it = iters ? iters : h->it_buf;
     int32_t *stt = status ? status : h->st_buf;
     // 1. the solve, dispatched in the caller's order (checked to be a permutation; ignored otherwise)
-    int32_t rc = solve_impl(h, B, p, w, w_sol, obj, stt, it, kkt, order, stream, obs, obs_stages);
+    int32_t rc = solve_impl(h, B, p, w, w_sol, obj, stt, it, kkt, order, stream, obs, obs_stages, duals);      // the multipliers of this period's w_sol
     if (rc != NMPC_OK) return rc;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
@@ -374,6 +381,53 @@ int32_t nmpc_eval_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const 
     P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
     P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
     hipError_t e = nmpc::launch_eval(P, h->cfg.m, B, p, w, f, g, (hipStream_t)stream, true);
+    return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+// the obstacle arguments of the *_duals calls and nmpc_kkt_batch: (NULL, 0) = the handle's own field, else those of the *_obs calls
+static int32_t opt_field_check(const nmpc_handle_t *h, int32_t B, const double *obs, int32_t obs_stages)
+{
+    if (!h) return NMPC_E_ARG;
+    return (!obs && obs_stages == 0) ? NMPC_OK : obs_field_check(h, B, obs, obs_stages);
+}
+
+int32_t nmpc_solve_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
+                               double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order, const nmpc_duals_t *duals, void *stream)
+{
+    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    int32_t rc = opt_field_check(h, B, obs, obs_stages);
+    if (rc != NMPC_OK) return rc;
+    if (h->kernel != 3) return NMPC_E_UNSUPPORTED;
+    return solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
+}
+
+int32_t nmpc_step_batch_duals(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *obs, int32_t obs_stages, double *obj,
+                              int32_t *status, int32_t *iters, double *kkt, int32_t *order, const nmpc_duals_t *duals, void *stream)
+{
+    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    int32_t rc = opt_field_check(h, B, obs, obs_stages);
+    if (rc != NMPC_OK) return rc;
+    if (h->kernel != 3) return NMPC_E_UNSUPPORTED;
+    return step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
+}
+
+int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                       const double *lam_x, double *res, double *grad_lag, void *stream)
+{
+    if (!h || B < 0) return NMPC_E_ARG;
+    int32_t rc = opt_field_check(h, B, obs, obs_stages);
+    if (rc != NMPC_OK) return rc;
+    if (B == 0) return NMPC_OK;
+    if (!p || !w || !lam_g || !lam_x || !res) return NMPC_E_ARG;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    nmpc::KParams P = h->P;
+    if (obs) {
+        P.ofield.ptr = obs;
+        P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
+        P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
+    }
+    hipError_t e = nmpc::launch_kkt(P, h->cfg.m, B, p, w, lam_g, lam_x, res, grad_lag, (hipStream_t)stream, obs != nullptr);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 

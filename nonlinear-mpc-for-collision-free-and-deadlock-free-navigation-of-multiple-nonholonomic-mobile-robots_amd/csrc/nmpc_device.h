@@ -30,6 +30,7 @@ struct KParams {
     int32_t pairs;        // 1: pair rows present (C6:288-306); 0: multi-robot NLP without them (mpc_online_casadi_tb3_multi_centralized.py)
     const int32_t *order;       // per call: dispatch order (workgroup g solves instance order[g]) or nullptr = identity
     const int32_t *order_bad;   // device flag written by the permutation check of that order: non-zero -> the hint is ignored
+    double *lam_g, *lam_x, *lam_p;      // per call (column kernel, nmpc_*_batch_duals): the multipliers of the returned point, [B][ng] / [B][nvar] / [B][2 nx], each or all nullptr
     int64_t stride2;      // workspace stride of the LDS-resident kernel (stage packs + transposed gains)
     int64_t oPACK, oKT;
     int64_t oCKPT;        // LDS-resident kernels: cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep, [(N-1)/NMPC_CKPT_EVERY + 1] slots of (3m + 1) * 64 doubles
@@ -61,6 +62,9 @@ hipError_t launch_solve_col_obs(const KParams &P, int m, int B, const double *p,
 size_t col_kernel_bytes(const KParams &P, int m, int shape);
 void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride);
 hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
+// KKT residuals of (w, lam_g, lam_x): res [B][6] = (stat, eq, ineq, bnd, compl, sign), grad_lag [B][nvar] or nullptr (include/nmpc.h, nmpc_kkt_batch)
+hipError_t launch_kkt(const KParams &P, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
+                      hipStream_t st, bool ofield);
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);
 hipError_t launch_odometry(long n, const double *odom, const double *init, double *pose, int wrap, hipStream_t st);

@@ -933,6 +933,90 @@ __global__ __launch_bounds__(256) void eval_kernel(const KParams P, int B, const
     if (f_out) atomicAdd(&f_out[b], fs);   // <= N adds per instance; order-dependent in the last bits only
 }
 
+// ------------------------------------------------------------------------------------------
+// KKT residuals of (w, lam_g, lam_x) in CasADi's convention L = f + lam_g' g + lam_x' w (include/nmpc.h, nmpc_kkt_batch): streaming, one
+// thread per (instance, stage) as eval_kernel, MS as there.  Thread k forms the gradient of L in X_k and U_k from the rows that touch them —
+// defects k-1 and k, the pair and obstacle rows of stage k (stage 0 included, with whatever multipliers it is given), for k = 0 the initial
+// block — and the residuals of the rows and variables of its stage; the six numbers of an instance are maxima of non-negative doubles,
+// reduced with an integer atomic max on their bit patterns (same order; a NaN ranks above every number, so it reaches the result).
+__device__ __forceinline__ void kkt_max(double &a, double v) { a = (v > a || v != v) ? v : a; }      // a starts at 0: the positive part; fmax would drop a NaN
+template <int MS>
+__global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, int B, const double *__restrict__ p_in, const double *__restrict__ w,
+                                                            const double *__restrict__ lam_g, const double *__restrict__ lam_x,
+                                                            double *__restrict__ res_out, double *__restrict__ grad_out)
+{
+    constexpr int M_ = MS % NMPC_EVAL_OBS, OS = MS / NMPC_EVAL_OBS;
+    constexpr int NX = Geo<M_>::NX, NU = Geo<M_>::NU, NP = Geo<M_>::NP;
+    const int N = P.N;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = (long)B * (N + 1);
+    if (gid >= total) return;
+    const int b = (int)(gid / (N + 1)), k = (int)(gid - (long)b * (N + 1));
+    const double *X = w + (size_t)b * P.nvar, *U = X + (size_t)(N + 1) * NX, *pp = p_in + (size_t)b * 2 * NX;
+    const double *lg = lam_g + (size_t)b * P.ng, *lxX = lam_x + (size_t)b * P.nvar + (size_t)k * NX, *lxU = lam_x + (size_t)b * P.nvar + (size_t)(N + 1) * NX + (size_t)k * NU;
+    double *gX = grad_out ? grad_out + (size_t)b * P.nvar + (size_t)k * NX : nullptr;
+    double *gU = grad_out ? grad_out + (size_t)b * P.nvar + (size_t)(N + 1) * NX + (size_t)k * NU : nullptr;
+    const double *x = X + (size_t)k * NX;
+    const double *lk = lg + P.rows0 + (size_t)k * P.rowsk;            // multipliers of stage k's block: defect k, pair rows, obstacle rows (k < N)
+    const double *lprev = lk - P.rowsk;                                // defect k-1 (k >= 1)
+    const int npairs = P.pairs ? NP : 0;
+    const ObsField<OS> OB(P, (size_t)b);
+    double stat = 0.0, eq = 0.0, ineq = 0.0, bnd = 0.0, cmp = 0.0, sgn = 0.0;
+    auto row = [&](double l, double gv, double lb) {                   // one inequality row g >= lb with multiplier l
+        kkt_max(ineq, lb - gv); kkt_max(cmp, fabs(l) * (gv - lb)); kkt_max(sgn, l);
+    };
+    auto var = [&](double v, double l, double ub) {                    // one variable -ub <= v <= ub with multiplier l; ub = +inf: no bound
+        kkt_max(bnd, -ub - v); kkt_max(bnd, v - ub);
+        if (ub < INFINITY) { kkt_max(cmp, fmax(-l, 0.0) * (v + ub)); kkt_max(cmp, fmax(l, 0.0) * (ub - v)); }
+    };
+    if (k == 0 && P.pad_rows && P.pairs)
+        for (int c = 0; c < NP; c++) row(lg[NX + c], P.pad_value, P.dmin2);
+#pragma unroll 1
+    for (int i = 0; i < M_; i++) {
+        const double xi = x[3 * i], yi = x[3 * i + 1], th = x[3 * i + 2];
+        double g0 = lxX[3 * i], g1 = lxX[3 * i + 1], g2 = lxX[3 * i + 2];
+        var(xi, g0, P.xymax); var(yi, g1, P.xymax); var(th, g2, P.thb ? P.thmax : INFINITY);
+        if (k == 0) {
+            g0 += lg[3 * i]; g1 += lg[3 * i + 1]; g2 += lg[3 * i + 2];
+            kkt_max(eq, fabs(xi - pp[3 * i])); kkt_max(eq, fabs(yi - pp[3 * i + 1])); kkt_max(eq, fabs(th - pp[3 * i + 2]));
+        } else {
+            g0 += lprev[3 * i]; g1 += lprev[3 * i + 1]; g2 += lprev[3 * i + 2];
+        }
+        if (k < N) {
+            const double *xn = x + NX, *u = U + (size_t)k * NU + 2 * i;
+            const double l0 = lk[3 * i], l1 = lk[3 * i + 1], l2 = lk[3 * i + 2], v = u[0], om = u[1];
+            double s, c;
+            sincos(th, &s, &c);
+            g0 += 2.0 * P.q[0] * (xi - pp[NX + 3 * i]) - l0;
+            g1 += 2.0 * P.q[1] * (yi - pp[NX + 3 * i + 1]) - l1;
+            g2 += 2.0 * P.q[2] * (th - pp[NX + 3 * i + 2]) - l2 + P.T * v * (s * l0 - c * l1);
+            kkt_max(eq, fabs(xn[3 * i] - (xi + P.T * v * c))); kkt_max(eq, fabs(xn[3 * i + 1] - (yi + P.T * v * s))); kkt_max(eq, fabs(xn[3 * i + 2] - (th + P.T * om)));
+            for (int j = 0; j < (P.pairs ? M_ : 0); j++) {
+                if (j == i) continue;
+                const int q = i < j ? pair_index<M_>(i, j) : pair_index<M_>(j, i);
+                const double dx = xi - x[3 * j], dy = yi - x[3 * j + 1], l = lk[NX + q];
+                g0 += 2.0 * dx * l; g1 += 2.0 * dy * l;
+                if (i < j) row(l, dx * dx + dy * dy, P.dmin2);
+            }
+            for (int o = 0; o < P.K; o++) {
+                const double dx = xi - OB(k, o, 0), dy = yi - OB(k, o, 1), rr = sqrt(dx * dx + dy * dy), l = lk[NX + npairs + i * P.K + o];
+                g0 += dx / rr * l; g1 += dy / rr * l;
+                row(l, rr - P.robdim - OB(k, o, 2), P.margin);
+            }
+            const double gv = 2.0 * P.r[0] * v + lxU[2 * i] - P.T * (c * l0 + s * l1), gw = 2.0 * P.r[1] * om + lxU[2 * i + 1] - P.T * l2;
+            var(v, lxU[2 * i], P.vmax); var(om, lxU[2 * i + 1], P.wmax);
+            kkt_max(stat, fabs(gv)); kkt_max(stat, fabs(gw));
+            if (gU) { gU[2 * i] = gv; gU[2 * i + 1] = gw; }
+        }
+        kkt_max(stat, fabs(g0)); kkt_max(stat, fabs(g1)); kkt_max(stat, fabs(g2));
+        if (gX) { gX[3 * i] = g0; gX[3 * i + 1] = g1; gX[3 * i + 2] = g2; }
+    }
+    unsigned long long *r = reinterpret_cast<unsigned long long *>(res_out + (size_t)b * 6);
+    const double six[6] = {stat, eq, ineq, bnd, cmp, sgn};
+#pragma unroll
+    for (int c = 0; c < 6; c++) atomicMax(&r[c], (unsigned long long)__double_as_longlong(six[c]));
+}
+
 // warm-start shift (C6:160-169,460-465) + optional plant step (casadi_test.py:17-26)
 template <int M_>
 __global__ __launch_bounds__(256) void shift_kernel(const KParams P, int B, const double *p_in, const double *__restrict__ w_in,
@@ -993,6 +1077,18 @@ template <int M_> static hipError_t launch_eval_m(const KParams &P, int B, const
         hipLaunchKernelGGL((eval_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
     else
         hipLaunchKernelGGL((eval_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
+    return hipGetLastError();
+}
+template <int M_> static hipError_t launch_kkt_m(const KParams &P, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res,
+                                                 double *grad_lag, hipStream_t st, bool ofield)
+{
+    hipError_t e = hipMemsetAsync(res, 0, sizeof(double) * 6 * (size_t)B, st);      // the maxima start at +0
+    if (e != hipSuccess) return e;
+    long total = (long)B * (P.N + 1);
+    if (ofield)
+        hipLaunchKernelGGL((kkt_residual_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, lam_g, lam_x, res, grad_lag);
+    else
+        hipLaunchKernelGGL((kkt_residual_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, lam_g, lam_x, res, grad_lag);
     return hipGetLastError();
 }
 template <int M_> static hipError_t launch_shift_m(const KParams &P, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st)
@@ -1120,6 +1216,13 @@ bool select_solve(const KParams &, int m, int, SolveVariant *v)
 hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
 {
 #define C_(M) launch_eval_m<M>(P, B, p, w, f, g, st, ofield)
+    NMPC_DISPATCH(m, C_)
+#undef C_
+}
+hipError_t launch_kkt(const KParams &P, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
+                      hipStream_t st, bool ofield)
+{
+#define C_(M) launch_kkt_m<M>(P, B, p, w, lam_g, lam_x, res, grad_lag, st, ofield)
     NMPC_DISPATCH(m, C_)
 #undef C_
 }

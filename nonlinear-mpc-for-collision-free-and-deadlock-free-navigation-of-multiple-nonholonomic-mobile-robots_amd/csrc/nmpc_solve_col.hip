@@ -178,6 +178,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     // slacks and duals of the inequality rows are only ever visited by the stage-parallel phases (coalesced, each lane its own
     // items) and live in the instance's workspace in HBM/L2 — that is what lets two instances share a SIMD (<= 20 KB of LDS each)
     extern __shared__ double sm[];
+    // (the epilogue that writes the multipliers locates X, U, LAM, SN, CS, XS and the dual arrays a second time by this carve-up: change both)
     double *X = sm;                       // [N1*NX]
     double *U = X + N1 * NX;              // [N*NU]
     double *LAM = U + N * NU;             // [N1*NX]   lam[k] pairs with defect c_{k-1}
@@ -294,6 +295,9 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         if (bad > 0.0) {
             for (int e = tid; e < N1 * NX; e += TPB) wo[e] = X[e];
             for (int e = tid; e < N * NU; e += TPB) wo[(size_t)N1 * NX + e] = U[e];
+            if (P.lam_g) for (int e = tid; e < P.ng; e += TPB) P.lam_g[inst * (size_t)P.ng + e] = 0.0;      // no iteration, no multipliers: zero rows
+            if (P.lam_x) for (int e = tid; e < P.nvar; e += TPB) P.lam_x[inst * (size_t)P.nvar + e] = 0.0;
+            if (P.lam_p) for (int e = tid; e < 2 * NX; e += TPB) P.lam_p[inst * (size_t)(2 * NX) + e] = 0.0;
             if (tid == 0) {
                 if (obj_out) obj_out[inst] = NAN;
                 if (status_out) status_out[inst] = NMPC_STATUS_INFEASIBLE_X0;
@@ -1624,6 +1628,55 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     __syncthreads();
     for (int e = tid; e < N1 * NX; e += TPB) wo[e] = X[e];
     for (int e = tid; e < N * NU; e += TPB) wo[(size_t)N1 * NX + e] = U[e];
+    // ---- the multipliers of the returned point in CasADi's layout and sign (include/nmpc.h, nmpc_solve_batch_duals): L = f + lam_g' g + lam_x' w
+    //      + lam_p' p.  One wave-uniform test of the pointers, nothing on the plain path.  The block locates the instance's arrays AGAIN, by the
+    //      carve-up at the top of the kernel, from N and K passed through an empty asm: otherwise the compiler keeps the main loop's bases and
+    //      offsets alive for it in scalar registers the loop has none to spare of (they spill into vector registers: six robots +2 VGPRs and 8..12 B of
+    //      scratch, two robots with the field 257 VGPRs).
+    //      The duals are read where this instantiation keeps them (LDS, or the instance's workspace: the barrier above has drained its stores).
+    if (P.lam_g || P.lam_x || P.lam_p) {
+        int Ne = P.N, Ke = P.K;
+        asm volatile("" : "+s"(Ne), "+s"(Ke));
+        const int N1e = Ne + 1, MKe = M_ * Ke;
+        const double *Xe = sm, *Ue = Xe + N1e * NX, *LAMe = Ue + Ne * NU, *SNe = LAMe + N1e * NX, *CSe = SNe + Ne * M_;
+        const double *RVe = CSe + Ne * M_ + N1e * NX + Ne * NU, *XSe = RVe + ((N1e * NX > RG0) ? N1e * NX : RG0);
+        double *gde = DLL ? const_cast<double *>(XSe) + NX + 8 : ws + inst * P.stride2 + P.oDUAL;
+        const int eZPp = N1e * NP, eZO = eZPp + N1e * NP + N1e * MKe, eZUL = eZO + N1e * MKe, eZUU = eZUL + Ne * NU, eZXL = eZUU + Ne * NU, eZXU = eZXL + N1e * NXB;
+        const UArr zp{gde, eZPp}, zo{gde, eZO}, zul{gde, eZUL}, zuu{gde, eZUU}, zxl{gde, eZXL}, zxu{gde, eZXU};
+        double *lg = P.lam_g ? P.lam_g + inst * (size_t)P.ng : nullptr;
+        double *lp = P.lam_p ? P.lam_p + inst * (size_t)(2 * NX) : nullptr;
+        // initial block X_0 - x0: from stationarity in X_0 (the stage-0 pair / obstacle rows carry 0); lam_p = (the same, 2 Q sum_k (X_k - xs))
+        for (int c = tid; c < NX; c += TPB) {
+            const int i = c / 3, d = c - 3 * i;
+            const double *ln = LAMe + NX + 3 * i;
+            double a = ln[d];
+            if (d == 2) { const double tv = P.T * Ue[2 * i]; a += (-tv * SNe[i]) * ln[0] + (tv * CSe[i]) * ln[1]; }
+            const double v = a - 2.0 * P.q[d] * (Xe[c] - XSe[c]);
+            if (lg) lg[c] = v;
+            if (lp) {
+                double s = 0.0;
+                for (int k = 0; k < Ne; k++) s += Xe[k * NX + c] - XSe[c];
+                lp[c] = v; lp[NX + c] = 2.0 * P.q[d] * s;
+            }
+        }
+        if (lg) {
+            const int r0 = P.rows0, rk = P.rowsk, npa = P.pairs ? NP : 0;
+            for (int e = NX + tid; e < r0; e += TPB) lg[e] = 0.0;      // pad rows
+            for (int it = tid; it < Ne * NX; it += TPB) { const int k = it / NX; lg[r0 + k * rk + (it - k * NX)] = LAMe[NX + it]; }      // defect k: LAM[k + 1]
+            for (int it = tid; it < Ne * npa; it += TPB) { const int k = it / NPd; lg[r0 + k * rk + NX + (it - k * NP)] = k ? -zp[it] : 0.0; }
+            for (int it = tid; it < Ne * MKe; it += TPB) { const int k = it / MKe; lg[r0 + k * rk + NX + npa + (it - k * MKe)] = k ? -zo[it] : 0.0; }
+        }
+        if (P.lam_x) {
+            double *lx = P.lam_x + inst * (size_t)P.nvar;
+            for (int e = tid; e < N1e * NX; e += TPB) {
+                const int k = e / NX, c = e - k * NX, i = c / 3, d = c - 3 * i;
+                double v = 0.0;      // X_0 is pinned by its equality rows; a heading without a bound has no multiplier
+                if (k >= 1 && (d < 2 || THB)) { const int s = k * NXB + (2 + THB) * i + d; v = zxu[s] - zxl[s]; }
+                lx[e] = v;
+            }
+            for (int e = tid; e < Ne * NU; e += TPB) lx[N1e * NX + e] = zuu[e] - zul[e];
+        }
+    }
     if (tid == 0) {
         if (obj_out) obj_out[inst] = f;
         if (status_out) status_out[inst] = status;

@@ -145,14 +145,28 @@ class NmpcSolver:
             raise ValueError(f"obstacles must have shape ({B}, {K}, 3) or ({B}, {N}, {K}, 3), got {tuple(o.shape)}")
         return o.contiguous(), int(o.shape[1])
 
+    def _duals(self, B):
+        """the multiplier outputs of a *_duals call: dict(lam_g [B, n_g], lam_x [B, n_var], lam_p [B, n_p]) of device tensors and their nmpc_duals_t"""
+        torch = self.torch
+        t = dict(lam_g=torch.empty((B, self.n_g), dtype=torch.float64, device=self.device),
+                 lam_x=torch.empty((B, self.n_var), dtype=torch.float64, device=self.device),
+                 lam_p=torch.empty((B, self.n_p), dtype=torch.float64, device=self.device))
+        return t, _lib.CDuals(t["lam_g"].data_ptr(), t["lam_x"].data_ptr(), t["lam_p"].data_ptr())
+
+    def duals_supported(self) -> bool:
+        """whether this handle returns multipliers (it runs on the column-per-lane kernel): nmpc_solve_batch_duals answers an empty batch"""
+        return self.lib.nmpc_solve_batch_duals(self._h, 0, None, None, 0, None, None, None, None, None, None, None, None, None) == 0
+
     # ---- batched device API -----------------------------------------------------------------
-    def solve_batch(self, p, w0, want_fg: bool = False, order=None, obstacles=None):
+    def solve_batch(self, p, w0, want_fg: bool = False, order=None, obstacles=None, want_duals: bool = False):
         """p [B, 2 n_x], w0 [B, n_var] (torch cuda / numpy) -> dict of torch cuda tensors.
 
         order: optional permutation of range(B) (dispatch-order hint, nmpc_solve_batch_ordered): workgroup g solves instance
         order[g]; put the instances expected to need the most iterations first.  Results are unaffected.
         obstacles: optional per-instance obstacle field (nmpc_solve_batch_obs), [B, K, 3] static or [B, N, K, 3] per stage (entry k: the
-        obstacles at the time of X_k), K = len(cfg.obstacles); the config's coordinates are then not used."""
+        obstacles at the time of X_k), K = len(cfg.obstacles); the config's coordinates are then not used.
+        want_duals: also return the multipliers of the returned point, lam_g [B, n_g], lam_x [B, n_var], lam_p [B, n_p], in CasADi's layout
+        and sign (nmpc_solve_batch_duals, include/nmpc.h); the other results do not depend on it."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w0 = self._dev(w0, (B, self.n_var))
@@ -164,8 +178,19 @@ class NmpcSolver:
         kkt = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device)
         iters = torch.empty(B, dtype=torch.int32, device=self.device)
+        lam = {}
         with torch.cuda.device(self.device):
-            if ob is not None:
+            if want_duals:
+                od = None
+                if order is not None:
+                    od = torch.as_tensor(order, device=self.device).to(torch.int32).contiguous()
+                    if od.shape != (B,):
+                        raise ValueError(f"order must have shape ({B},)")
+                lam, cd = self._duals(B)
+                _lib.check(self.lib.nmpc_solve_batch_duals(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
+                                                           w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
+                                                           od.data_ptr() if od is not None else None, C.byref(cd), self._stream()), "nmpc_solve_batch_duals")
+            elif ob is not None:
                 od = None
                 if order is not None:
                     od = torch.as_tensor(order, device=self.device).to(torch.int32).contiguous()
@@ -183,18 +208,19 @@ class NmpcSolver:
                     raise ValueError(f"order must have shape ({B},)")
                 _lib.check(self.lib.nmpc_solve_batch_ordered(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(),
                                                              iters.data_ptr(), kkt.data_ptr(), od.data_ptr(), self._stream()), "nmpc_solve_batch_ordered")
-        out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt)
+        out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt, **lam)
         if want_fg:
             f, g = self.eval_batch(p, w, obstacles=ob[0] if ob is not None else None)
             out["f"], out["g"] = f, g
         return out
 
-    def step_batch(self, p, w, order=None, obstacles=None):
+    def step_batch(self, p, w, order=None, obstacles=None, want_duals: bool = False):
         """One control period on the device (nmpc_step_batch): solve from the guess w, then IN PLACE w <- shifted solution and
         p[:, :n_x] <- x0 + T f(x0, u_0); `order` [B] int32 device tensor (in: dispatch order of this period, out: the order for the
         next one, sorted by this period's iteration counts, longest first) or None.  p and w must be contiguous float64 device
         tensors owned by the caller (they are modified).  Returns sol['x'] of this period and the per-instance outputs.
-        obstacles: optional per-instance obstacle field of this period (nmpc_step_batch_obs), as in solve_batch."""
+        obstacles: optional per-instance obstacle field of this period (nmpc_step_batch_obs), as in solve_batch.
+        want_duals: also return lam_g, lam_x, lam_p of this period's solution (nmpc_step_batch_duals), as in solve_batch."""
         torch = self.torch
         B = p.shape[0]
         if not (torch.is_tensor(p) and torch.is_tensor(w) and p.is_cuda and w.is_cuda and p.dtype == torch.float64 and w.dtype == torch.float64
@@ -209,6 +235,12 @@ class NmpcSolver:
         obj = torch.empty(B, dtype=torch.float64, device=self.device); kkt = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device); iters = torch.empty(B, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
+            if want_duals:
+                lam, cd = self._duals(B)
+                _lib.check(self.lib.nmpc_step_batch_duals(self._h, B, p.data_ptr(), w.data_ptr(), x.data_ptr(), ob[0].data_ptr() if ob is not None else None,
+                                                          ob[1] if ob is not None else 0, obj.data_ptr(), status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
+                                                          order.data_ptr() if order is not None else None, C.byref(cd), self._stream()), "nmpc_step_batch_duals")
+                return dict(x=x, f=obj, status=status, iters=iters, kkt=kkt, order=order, **lam)
             if ob is not None:
                 _lib.check(self.lib.nmpc_step_batch_obs(self._h, B, p.data_ptr(), w.data_ptr(), x.data_ptr(), ob[0].data_ptr(), ob[1], obj.data_ptr(),
                                                         status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
@@ -233,6 +265,22 @@ class NmpcSolver:
                 return f, g
             _lib.check(self.lib.nmpc_eval_batch(self._h, B, p.data_ptr(), w.data_ptr(), f.data_ptr(), g.data_ptr(), self._stream()), "nmpc_eval_batch")
         return f, g
+
+    def kkt_batch(self, p, w, lam_g, lam_x, obstacles=None, want_grad: bool = False):
+        """KKT residuals of (w, lam_g, lam_x) for B instances on the device (nmpc_kkt_batch): res [B, 6] = (stat, eq, ineq, bnd, compl, sign) as
+        include/nmpc.h defines them, and with want_grad also grad_lag [B, n_var] = grad f + J' lam_g + lam_x.  The multipliers may be a solve's
+        (want_duals=True) or any others; obstacles as in solve_batch.  Works on every handle."""
+        torch = self.torch
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
+        res = torch.empty((B, 6), dtype=torch.float64, device=self.device)
+        grad = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device) if want_grad else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nmpc_kkt_batch(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
+                                               w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), res.data_ptr(), grad.data_ptr() if want_grad else None,
+                                               self._stream()), "nmpc_kkt_batch")
+        return (res, grad) if want_grad else res
 
     def shift_batch(self, p, w, plant: bool = True):
         """device warm-start shift (C6:160-169,460-465) and, if plant, x0 + T f(x0,u0) (casadi_test.py:17-26)."""
@@ -268,12 +316,16 @@ class NmpcSolver:
                 raise ValueError(f"{name} has {g.size} entries, expected {want.size}")
             if not np.array_equal(g, want):
                 raise ValueError(f"{name} differs from the bounds of the configured problem; build a new config instead")
-        r = self.solve_batch(p[None, :], w0[None, :], want_fg=True)
+        duals = self.duals_supported()      # the handle's kernel has the multipliers (sol['lam_g'], sol['lam_x'], sol['lam_p']) or the keys are absent
+        r = self.solve_batch(p[None, :], w0[None, :], want_fg=True, want_duals=duals)
         self.torch.cuda.synchronize(self.device)
         st = int(r["status"][0])
         self._stats = dict(return_status=_lib.STATUS_NAMES.get(st, str(st)), success=(st == 0), iter_count=int(r["iters"][0]),
                            kkt_error=float(r["kkt"][0]), status_code=st)
-        return {"x": r["x"][0].cpu().numpy().reshape(-1, 1), "f": float(r["f"][0]), "g": r["g"][0].cpu().numpy().reshape(-1, 1)}
+        sol = {"x": r["x"][0].cpu().numpy().reshape(-1, 1), "f": float(r["f"][0]), "g": r["g"][0].cpu().numpy().reshape(-1, 1)}
+        if duals:
+            sol.update({k: r[k][0].cpu().numpy().reshape(-1, 1) for k in ("lam_g", "lam_x", "lam_p")})
+        return sol
 
     def stats(self) -> Dict:
         """CasADi's solver.stats(); the reference never reads it, non-convergence is reported here only."""
