@@ -7,6 +7,7 @@
 #define NMPC_DEBUG_H_
 
 #include "nmpc.h"
+#include "nmpc_lidar.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -35,6 +36,18 @@ typedef struct nmpc_debug_variant {
 /* the instantiation a solve of B instances on this handle would launch (ordered != 0: with a dispatch-order hint; obs_field != 0: an *_obs call).
    No launch is made.  Returns NMPC_OK, NMPC_E_ARG, or NMPC_E_UNSUPPORTED where the call itself would. */
 int32_t nmpc_debug_variant(const nmpc_handle_t *h, int32_t B, int32_t ordered, int32_t obs_field, nmpc_debug_variant_t *out);
+
+/* the kernel instantiation of one LIDAR solve launch (include/nmpc_lidar.h), as in its mangled name: lidar_solve_kernelILi{rays}ELi{waves}E */
+typedef struct nmpc_debug_lidar_variant {
+    int32_t rays;           /* template ray count: 10 (the scripts' count, loops unrolled for it) or -1 (any other count, predicated) */
+    int32_t waves;          /* register budget: resident waves per SIMD the instantiation is compiled for, 1 or 2 */
+    int32_t two_wave_above; /* the handle launches the two-wave build for B above this (4 x compute units); INT32_MAX where it never does (rays = -1) */
+    int32_t threads;        /* workgroup size: one wavefront per robot */
+    int64_t lds_bytes;      /* dynamic LDS of the launch */
+} nmpc_debug_lidar_variant_t;
+/* the instantiation nmpc_lidar_solve_batch() of B instances on this handle would launch, chosen by the function the call itself launches by.
+   No launch is made.  Returns NMPC_OK, or NMPC_E_ARG where the call itself would (null handle, B outside 0..max_batch) or out is null. */
+int32_t nmpc_debug_lidar_variant(const nmpc_lidar_handle_t *h, int32_t B, nmpc_debug_lidar_variant_t *out);
 
 #ifdef __cplusplus
 }

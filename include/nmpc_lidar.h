@@ -57,7 +57,8 @@ int32_t nmpc_lidar_destroy(nmpc_lidar_handle_t *h);
  *   obj, status, iters, kkt [B]  (may be NULL)
  * One wavefront per robot.  Batches up to one robot per SIMD (4 x the device's compute units) run the one-wave-per-SIMD build of the kernel (a lone
  * wave iterates fastest: the launch is its longest solve), larger ones the two-waves-per-SIMD build (the launch is the batch's work).  Results do not
- * depend on the choice.  Stream-ordered; a handle owns one workspace (two launches in flight need two handles).
+ * depend on the choice: the two builds return bit-identical outputs (asserted on an MI355X by tests/test_gpu_lidar_variants.py at the batch
+ * sizes either side of the switch).  Stream-ordered; a handle owns one workspace (two launches in flight need two handles).
  */
 int32_t nmpc_lidar_solve_batch(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj,
                                int32_t *status, int32_t *iters, double *kkt, void *stream);

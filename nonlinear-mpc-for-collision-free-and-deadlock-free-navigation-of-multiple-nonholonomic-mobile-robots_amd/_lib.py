@@ -20,7 +20,7 @@ ERRORS = {-1: "NMPC_E_ARG", -2: "NMPC_E_UNSUPPORTED", -3: "NMPC_E_HIP", -4: "NMP
 
 LIDAR_EXPORTS = ["nmpc_lidar_n_var", "nmpc_lidar_n_g", "nmpc_lidar_n_p", "nmpc_lidar_create", "nmpc_lidar_destroy", "nmpc_lidar_solve_batch",
                  "nmpc_lidar_eval_batch", "nmpc_lidar_shift_batch", "nmpc_lidar_scan_batch", "nmpc_lidar_plant_batch"]
-DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", "nmpc_debug_workspace", "nmpc_debug_variant"]      # include/nmpc_debug.h
+DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", "nmpc_debug_workspace", "nmpc_debug_variant", "nmpc_debug_lidar_variant"]      # include/nmpc_debug.h
 QUERY_KERNEL_FOR_BATCH, QUERY_WORKSPACE_BYTES, QUERY_LDS_BYTES, QUERY_MAX_BATCH, QUERY_KERNEL_FOR_ORDERED_BATCH = 1, 2, 3, 4, 5      # NMPC_QUERY_* of include/nmpc.h
 EXPORTS = ["nmpc_n_var", "nmpc_n_g", "nmpc_n_p", "nmpc_config_default", "nmpc_create", "nmpc_create_opts", "nmpc_query", "nmpc_destroy",
            "nmpc_workspace_bytes", "nmpc_solve_batch", "nmpc_solve_batch_ordered", "nmpc_step_batch", "nmpc_eval_batch", "nmpc_shift_batch", "nmpc_odometry_batch", "nmpc_version",
@@ -50,6 +50,11 @@ class CDuals(C.Structure):
 class CDebugVariant(C.Structure):
     """nmpc_debug_variant_t (include/nmpc_debug.h)"""
     _fields_ = [("kernel", C.c_int32), ("m", C.c_int32), ("thb", C.c_int32), ("flags", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+class CDebugLidarVariant(C.Structure):
+    """nmpc_debug_lidar_variant_t (include/nmpc_debug.h)"""
+    _fields_ = [("rays", C.c_int32), ("waves", C.c_int32), ("two_wave_above", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int64)]
 
 
 class CLidarConfig(C.Structure):
@@ -114,6 +119,7 @@ def load():
     L.nmpc_lidar_shift_batch.argtypes = [vp, i32, vp, vp, vp]; L.nmpc_lidar_shift_batch.restype = i32
     L.nmpc_lidar_scan_batch.argtypes = [C.c_int64, i32, i32, vp, vp, C.c_double, vp, vp]; L.nmpc_lidar_scan_batch.restype = i32
     L.nmpc_lidar_plant_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp]; L.nmpc_lidar_plant_batch.restype = i32
+    L.nmpc_debug_lidar_variant.argtypes = [vp, i32, C.POINTER(CDebugLidarVariant)]; L.nmpc_debug_lidar_variant.restype = i32
     _lib = L
     return L
 

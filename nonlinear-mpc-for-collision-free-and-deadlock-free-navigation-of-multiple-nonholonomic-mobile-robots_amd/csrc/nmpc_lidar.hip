@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "../../include/nmpc_constants.h"      // cold-start retry and inertia constants shared with the main solver and the oracles
 #include "../../include/nmpc_lidar.h"
+#include "../../include/nmpc_debug.h"
 
 namespace nmpc_lidar {
 
@@ -1175,6 +1176,23 @@ struct LidarDeviceScope {
     ~LidarDeviceScope() { if (switched) (void)hipSetDevice(prev); }
 };
 
+// The instantiation a solve of B instances launches: nmpc_lidar_solve_batch() launches by it, nmpc_debug_lidar_variant() reports it.
+// The ray count of the scripts gets its own instantiation (component loops unrolled, loads of a stage issued together); any other count
+// runs the predicated one.
+// Two register budgets of the ten-ray kernel: one wave per SIMD (no spill; a lone wave iterates fastest: batches that fit the machine, whose
+// launch is its longest solve) and two (256 registers, 68 spilled dwords outside the recursions: 5 instead of 4 instances per CU by LDS —
+// batches beyond one instance per SIMD, whose launch is the batch's work).  Measured (round 4, V4, mean of three): B = 4096 192 k -> 199 k
+// solves/s with the second, B = 1024 115 k -> 109 k.
+static void lidar_launch_choice(const nmpc_lidar_handle *h, int32_t B, nmpc_debug_lidar_variant_t *v)
+{
+    const bool ten = h->cfg.R == 10;
+    v->two_wave_above = ten ? 4 * h->n_cu : INT32_MAX;      // only the ten-ray kernel has a second budget
+    v->rays = ten ? 10 : -1;
+    v->waves = B > v->two_wave_above ? 2 : 1;
+    v->threads = 64;
+    v->lds_bytes = (int64_t)h->lds_bytes;
+}
+
 int32_t nmpc_lidar_solve_batch(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
                                int32_t *iters, double *kkt, void *stream)
 {
@@ -1183,18 +1201,22 @@ int32_t nmpc_lidar_solve_batch(nmpc_lidar_handle_t *h, int32_t B, const double *
     if (!p || !w0 || !w_out) return NMPC_E_ARG;
     LidarDeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
-    // the ray count of the scripts gets its own instantiation (component loops unrolled, loads of a stage issued together); any other count
-    // runs the predicated one.  The dynamic-LDS limit is an attribute of the kernel FUNCTION, not of a handle: set per launch when this
-    // handle needs more than HIP's default of 64 KB (a second handle with another horizon would otherwise change the limit under this one)
-    // Two register budgets of the ten-ray kernel: one wave per SIMD (no spill; a lone wave iterates fastest: batches that fit the machine, whose
-    // launch is its longest solve) and two (256 registers, 68 spilled dwords outside the recursions: 5 instead of 4 instances per CU by LDS —
-    // batches beyond one instance per SIMD, whose launch is the batch's work).  Measured (round 4, V4, mean of three): B = 4096 192 k -> 199 k
-    // solves/s with the second, B = 1024 115 k -> 109 k.
-    const bool crowded = B > 4 * h->n_cu;
-    auto kern = (h->cfg.R == 10) ? (crowded ? nmpc_lidar::lidar_solve_kernel<10, 2> : nmpc_lidar::lidar_solve_kernel<10, 1>) : nmpc_lidar::lidar_solve_kernel<-1, 1>;
+    nmpc_debug_lidar_variant_t v;
+    lidar_launch_choice(h, B, &v);
+    auto kern = (v.rays == 10) ? (v.waves == 2 ? nmpc_lidar::lidar_solve_kernel<10, 2> : nmpc_lidar::lidar_solve_kernel<10, 1>) : nmpc_lidar::lidar_solve_kernel<-1, 1>;
+    // The dynamic-LDS limit is an attribute of the kernel FUNCTION, not of a handle: set per launch when this handle needs more than HIP's
+    // default of 64 KB (a second handle with another horizon would otherwise change the limit under this one)
     if (h->lds_bytes > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) != hipSuccess) return NMPC_E_HIP;
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), h->lds_bytes, (hipStream_t)stream, h->P, B, p, w0, w_out, obj, status, iters, kkt, h->ws);
     return hipGetLastError() == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+/* include/nmpc_debug.h: the instantiation a solve of B instances on this handle would launch; no launch is made */
+int32_t nmpc_debug_lidar_variant(const nmpc_lidar_handle_t *h, int32_t B, nmpc_debug_lidar_variant_t *out)
+{
+    if (!h || !out || B < 0 || B > h->max_batch) return NMPC_E_ARG;
+    lidar_launch_choice(h, B, out);
+    return NMPC_OK;
 }
 
 int32_t nmpc_lidar_eval_batch(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w, double *f, double *g, void *stream)

@@ -213,3 +213,49 @@ def kernel_notes(tmp_path):
                     d[key] = int(m.group(1))
             res[name.group(1)] = d
     return res
+
+
+# ---- guarded raw C-ABI calls (tests/test_gpu_kernel_variants.py, tests/test_gpu_lidar_variants.py) ----------------------------------------
+GUARD = 64                              # sentinel elements before and after every output
+SENT64 = 0x7FF4DEADBEEF0123             # a NaN payload no solve produces
+SENT32 = 0x5A5A5A5A
+
+
+def _bits(t):
+    import torch
+    return t.view(torch.int32) if t.dtype == torch.int32 else t.view(torch.int64)
+
+
+def guarded_call(outs, ins, call):
+    """One C-ABI call with every output carved out of the middle of a larger sentinel-filled device array, made twice.
+    outs: {name: (elements, "f8" | "i4")}; ins: the device tensors the call reads; call(ptr) makes the call with the output pointers ptr[name]
+    and returns its code.  Asserts: the call returns 0 and leaves the bands around every output untouched; the inputs come back
+    bit-identical; a second call returns bit-identical outputs; no output element keeps the sentinel.  Returns the outputs of the first call as
+    numpy arrays (float64 / int32)."""
+    import torch
+    dev = ins[0].device
+    before = [t.clone() for t in ins]
+
+    def once():
+        bufs = {k: torch.full((2 * GUARD + n,), SENT64 if dt == "f8" else SENT32, dtype=torch.int64 if dt == "f8" else torch.int32, device=dev)
+                for k, (n, dt) in outs.items()}
+        ptr = {k: t.data_ptr() + GUARD * t.element_size() for k, t in bufs.items()}
+        rc = call(ptr)
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        out = {}
+        for k, t in bufs.items():
+            a = t.cpu().numpy()
+            sent = np.int64(SENT64) if a.dtype == np.int64 else np.int32(SENT32)
+            assert (a[:GUARD] == sent).all() and (a[-GUARD:] == sent).all(), "the call wrote outside its %s output" % k
+            out[k] = a[GUARD:-GUARD].copy()
+        return out
+    first = once()
+    for t, b in zip(ins, before):
+        assert torch.equal(_bits(t), _bits(b)), "the call changed one of its inputs"
+    second = once()
+    for k in first:
+        assert np.array_equal(first[k], second[k]), "a second call with the same inputs returned other bits in %s (state left in the workspace)" % k
+    for k, a in first.items():      # every output element was written, and none is the sentinel
+        assert not (a == (np.int64(SENT64) if a.dtype == np.int64 else np.int32(SENT32))).any(), k
+    return {k: (a.view(np.float64) if a.dtype == np.int64 else a) for k, a in first.items()}

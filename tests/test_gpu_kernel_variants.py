@@ -19,9 +19,6 @@ pytestmark = pytest.mark.gpu
 
 W_TOL = 1e-6
 F_RTOL = 1e-6
-GUARD = 64                              # sentinel elements before and after every output
-SENT64 = 0x7FF4DEADBEEF0123             # a NaN payload no solve produces
-SENT32 = 0x5A5A5A5A
 
 
 def _handle(cfg, max_iter, max_batch, pin):
@@ -42,52 +39,27 @@ def _variant(L, h, B, ordered, obs_field):
 
 
 def _abi_solve(L, h, cfg, P, W0, F, order):
-    """One nmpc_solve_batch / _ordered / _obs call with guarded outputs, twice.  Returns the outputs of the first call as numpy arrays."""
+    """One nmpc_solve_batch / _ordered / _obs call with guarded outputs, twice (helpers.guarded_call).  Returns the outputs of the first call
+    as numpy arrays."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     B, nvar = P.shape[0], W0.shape[1]
     p = torch.as_tensor(P, device=dev).contiguous(); w0 = torch.as_tensor(W0, device=dev).contiguous()
     od = torch.as_tensor(order, device=dev).to(torch.int32).contiguous() if order is not None else None
     ob = torch.as_tensor(F, device=dev).contiguous() if F is not None else None
-    ins = [t for t in (p, w0, od, ob) if t is not None]
-    before = [t.clone() for t in ins]
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-    def call():
-        bufs = dict(x=torch.full((2 * GUARD + B * nvar,), SENT64, dtype=torch.int64, device=dev),
-                    f=torch.full((2 * GUARD + B,), SENT64, dtype=torch.int64, device=dev),
-                    kkt=torch.full((2 * GUARD + B,), SENT64, dtype=torch.int64, device=dev),
-                    status=torch.full((2 * GUARD + B,), SENT32, dtype=torch.int32, device=dev),
-                    iters=torch.full((2 * GUARD + B,), SENT32, dtype=torch.int32, device=dev))
-        ptr = {k: t.data_ptr() + GUARD * t.element_size() for k, t in bufs.items()}
+    def call(ptr):
         if ob is not None:
-            rc = L.nmpc_solve_batch_obs(h, B, p.data_ptr(), ob.data_ptr(), int(ob.shape[1]), w0.data_ptr(), ptr["x"], ptr["f"], ptr["status"], ptr["iters"],
-                                        ptr["kkt"], od.data_ptr() if od is not None else None, stream)
-        elif od is not None:
-            rc = L.nmpc_solve_batch_ordered(h, B, p.data_ptr(), w0.data_ptr(), ptr["x"], ptr["f"], ptr["status"], ptr["iters"], ptr["kkt"], od.data_ptr(), stream)
-        else:
-            rc = L.nmpc_solve_batch(h, B, p.data_ptr(), w0.data_ptr(), ptr["x"], ptr["f"], ptr["status"], ptr["iters"], ptr["kkt"], stream)
-        assert rc == 0, rc
-        torch.cuda.synchronize()
-        out = {}
-        for k, t in bufs.items():
-            a = t.cpu().numpy()
-            sent = np.int64(SENT64) if a.dtype == np.int64 else np.int32(SENT32)
-            assert (a[:GUARD] == sent).all() and (a[-GUARD:] == sent).all(), "the call wrote outside its %s output" % k
-            out[k] = a[GUARD:-GUARD].copy()
-        return out
-    first = call()
-    for t, b in zip(ins, before):
-        assert torch.equal(t.view(torch.int32) if t.dtype == torch.int32 else t.view(torch.int64), b.view(torch.int32) if b.dtype == torch.int32 else b.view(torch.int64)), \
-            "the call changed one of its inputs"
-    second = call()
-    for k in first:
-        assert np.array_equal(first[k], second[k]), "a second call with the same inputs returned other bits in %s (state left in the workspace)" % k
-    for k in ("x", "f", "kkt"):      # every output element was written, and none is the sentinel
-        assert not (first[k] == np.int64(SENT64)).any(), k
-    assert not (first["status"] == np.int32(SENT32)).any() and not (first["iters"] == np.int32(SENT32)).any()
-    return dict(x=first["x"].view(np.float64).reshape(B, nvar), f=first["f"].view(np.float64), kkt=first["kkt"].view(np.float64),
-                status=first["status"], iters=first["iters"])
+            return L.nmpc_solve_batch_obs(h, B, p.data_ptr(), ob.data_ptr(), int(ob.shape[1]), w0.data_ptr(), ptr["x"], ptr["f"], ptr["status"], ptr["iters"],
+                                          ptr["kkt"], od.data_ptr() if od is not None else None, stream)
+        if od is not None:
+            return L.nmpc_solve_batch_ordered(h, B, p.data_ptr(), w0.data_ptr(), ptr["x"], ptr["f"], ptr["status"], ptr["iters"], ptr["kkt"], od.data_ptr(), stream)
+        return L.nmpc_solve_batch(h, B, p.data_ptr(), w0.data_ptr(), ptr["x"], ptr["f"], ptr["status"], ptr["iters"], ptr["kkt"], stream)
+    out = Hh.guarded_call(dict(x=(B * nvar, "f8"), f=(B, "f8"), kkt=(B, "f8"), status=(B, "i4"), iters=(B, "i4")),
+                          [t for t in (p, w0, od, ob) if t is not None], call)
+    out["x"] = out["x"].reshape(B, nvar)
+    return out
 
 
 def _order(B, seed):

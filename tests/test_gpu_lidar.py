@@ -8,31 +8,11 @@ import pytest
 
 from oracle import lidar_ref as LR, oracle_lib as O
 from tests import helpers as Hh
+from tests.lidar_variants import batch as _batch, world as _world      # noqa: F401  (the generator lives with the recipes that share it)
 
 pytestmark = pytest.mark.gpu
 
 W_TOL = 1e-6
-
-
-def _world(rng):
-    return [(float(rng.uniform(0.8, 2.6)), float(rng.uniform(0.3, 2.4)), float(rng.uniform(0.15, 0.3))) for _ in range(3)] + \
-           [(float(rng.uniform(-1.5, 0.5)), float(rng.uniform(-1.5, -0.5)), 0.2)]
-
-
-def _batch(cfg, B, seed, goal=(3.0, 2.5, 0.0)):
-    """robots near the origin looking into the first quadrant (the script's start, V4:184), synthetic scans of a random world of
-    circular obstacles, the script's first goal (V4:221)."""
-    rng = np.random.Generator(np.random.PCG64(20210141 + seed))
-    P, W0 = [], []
-    for _ in range(B):
-        if cfg.aligned_bounds:
-            pose = np.array([rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2), rng.uniform(-0.5, 1.2)])
-        else:       # the script's misaligned bounds force x, y, theta >= d_min from stage ~24 (V4) / ~29 (V3) on: start where that is reachable
-            pose = np.array([rng.uniform(0.0, 0.15), rng.uniform(0.0, 0.15), rng.uniform(0.4, 1.1)])
-        scan = LR.scan_of_world(pose, _world(rng), cfg.R)
-        xs = np.array(goal) + rng.uniform(-0.3, 0.3, 3)
-        P.append(LR.make_p(cfg, pose, xs, scan)); W0.append(LR.cold_start(cfg, np.concatenate([pose, scan])))
-    return np.stack(P), np.stack(W0)
 
 
 def _product(cfg, **kw):
