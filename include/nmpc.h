@@ -116,7 +116,8 @@ int32_t nmpc_create_opts(const nmpc_config_t *cfg, int32_t max_batch, const nmpc
  *   NMPC_QUERY_KERNEL_FOR_BATCH  arg = B: the solve kernel nmpc_solve_batch launches for a batch of B: 1 / 2 / 3 as in nmpc_options_t, 4 = the
  *                                column kernel's latency shape (two OR four wavefronts per instance: 5 is a pin, never an answer)
  *   NMPC_QUERY_WORKSPACE_BYTES   device workspace held by the handle (same as nmpc_workspace_bytes)
- *   NMPC_QUERY_LDS_BYTES         arg = B: dynamic LDS per swarm instance of the kernel an UNORDERED call of B gets (0 for the HBM-resident kernel's fixed carve-up)
+ *   NMPC_QUERY_LDS_BYTES         arg = B: dynamic LDS per swarm instance of the kernel an UNORDERED call of B gets (0 for the HBM-resident kernel's fixed
+ *                                carve-up; for the element-per-lane kernel the bytes of its throughput shape whatever B: its latency shapes take a little more)
  *   NMPC_QUERY_MAX_BATCH         the max_batch the handle was created for
  *   NMPC_QUERY_KERNEL_FOR_ORDERED_BATCH  arg = B: as NMPC_QUERY_KERNEL_FOR_BATCH for a call that carries a dispatch-order hint
  *                                (nmpc_solve_batch_ordered, nmpc_step_batch): the latency shape is kept for larger batches then

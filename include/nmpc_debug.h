@@ -36,6 +36,12 @@ typedef struct nmpc_debug_variant {
 /* the instantiation a solve of B instances on this handle would launch (ordered != 0: with a dispatch-order hint; obs_field != 0: an *_obs call).
    No launch is made.  Returns NMPC_OK, NMPC_E_ARG, or NMPC_E_UNSUPPORTED where the call itself would. */
 int32_t nmpc_debug_variant(const nmpc_handle_t *h, int32_t B, int32_t ordered, int32_t obs_field, nmpc_debug_variant_t *out);
+/* the same without a handle and without a device: the instantiation the handle nmpc_create_opts(cfg, max_batch >= B, opts) makes on a device
+   with compute_units compute units would launch, by the functions the handle itself chooses with.  *kernel (may be NULL) <- the kernel code
+   NMPC_QUERY_KERNEL_FOR_BATCH / _ORDERED_BATCH answers (1..4).  Returns the codes of nmpc_debug_variant, and those of nmpc_create_opts for
+   the configuration and the options (opts may be NULL). */
+int32_t nmpc_debug_variant_of_config(const nmpc_config_t *cfg, const nmpc_options_t *opts, int32_t compute_units, int32_t B, int32_t ordered,
+                                     int32_t obs_field, nmpc_debug_variant_t *out, int32_t *kernel);
 
 /* the kernel instantiation of one LIDAR solve launch (include/nmpc_lidar.h), as in its mangled name: lidar_solve_kernelILi{rays}ELi{waves}E */
 typedef struct nmpc_debug_lidar_variant {

@@ -10,21 +10,31 @@
 #include "nmpc_device.h"
 #include "../../include/nmpc_debug.h"
 
+// What create decides about the solve kernels of one configuration: pure arithmetic on (filled KParams, pin, compute units), no HIP call.
+// solve_plan() maps it and a call to the launch.
+struct Selector {
+    int pin;              // nmpc_options_t.kernel: 0 chosen per call, 1 / 2 / 3 that kernel, 4 / 5 the column kernel's latency shape with two / four wavefronts
+    int base;             // KERN_HBM / KERN_LDS / KERN_COL: the pin, or the column kernel, after the fallbacks for horizons beyond the LDS
+    bool lds_fits;        // the element-per-lane kernel fits the LDS for this configuration
+    bool lat_fits;        // the column kernel's latency shape (two wavefronts per instance, duals in LDS up to six robots) fits the LDS
+    int32_t lat_slots;    // instances of that shape the device holds at once
+    int32_t lat_slots4;   // the same for four wavefronts per instance (2 per CU at 256 VGPRs per wave)
+};
+// the launch of one solve call: kernel code (KERN_*: what NMPC_QUERY_KERNEL_FOR_BATCH answers), the column kernel's shape and the instantiation
+struct SolvePlan {
+    int kernel, shape;
+    nmpc::SolveVariant v;
+};
+
 struct nmpc_handle {
     nmpc_config_t cfg;
     nmpc::KParams P;
+    Selector sel;
     int32_t max_batch;
     double *ws;          // device workspace: max_batch * stride doubles
     int64_t ws_bytes;
-    int kernel;          // 3 = column-per-lane LDS-resident kernel (default), 2 = element-per-lane LDS-resident kernel, 1 = HBM-resident workgroup kernel, 4 = 3 pinned to its latency shape
     long long *prof;     // device counters of the NMPC_PROFILE build (12 x int64), else unused
     int device;          // device the workspace lives on; made current for the duration of every call
-    bool lat_ok;         // the element-per-lane kernel's latency shapes fit the LDS for this configuration
-    int col_lat;         // column kernel shape pin: 1 latency, -1 throughput, 0 by batch size
-    bool col_lat_ok;     // the column kernel's latency shape (two wavefronts per instance, duals in LDS up to six robots) fits the LDS
-    int32_t lat_slots;   // instances of that shape the device holds at once
-    int32_t lat_slots4;  // the same for four wavefronts per instance (2 per CU at 256 VGPRs per wave)
-    int lat_waves;       // 0: two or four wavefronts by the rule of lat_waves_shape(); 2 / 4: pinned (nmpc_options_t.kernel = 4 / 5)
     int32_t *ord_chk;    // [max_batch + 1] permutation check of a dispatch-order hint: counts, then the "bad" flag
     int32_t *it_buf;     // [max_batch] iteration counts of nmpc_step_batch when the caller passes iters == NULL
     int32_t *st_buf;     // [max_batch] statuses of nmpc_step_batch when the caller passes status == NULL (the in-place update skips failed instances)
@@ -42,6 +52,9 @@ struct DeviceScope {
 };
 
 static bool m_supported(int m) { return m >= 1 && m <= NMPC_MAX_ROBOTS; }      // every team size 1..10 is instantiated (7 and 9 since round 4)
+using nmpc::KERN_HBM; using nmpc::KERN_LDS; using nmpc::KERN_COL; using nmpc::KERN_COL_LAT;
+using nmpc::SHAPE_TP; using nmpc::SHAPE_LAT2; using nmpc::SHAPE_LAT4;
+static const size_t LDS_PER_CU = (size_t)160 * 1024;
 
 extern "C" {
 
@@ -66,7 +79,7 @@ void nmpc_config_default(nmpc_config_t *c, int32_t m, int32_t N)
     c->tol = 1e-8; c->mu_init = 0.5; c->max_iter = 2000; c->pair_rows = 1;
 }
 
-static int fill_params(const nmpc_config_t *c, nmpc::KParams *P)
+static void fill_params(const nmpc_config_t *c, nmpc::KParams *P)
 {
     memset(P, 0, sizeof(*P));
     const int m = c->m, N = c->N, nx = 3 * m, nu = 2 * m, M = c->pair_rows ? m * (m - 1) / 2 : 0, K = c->n_obs;
@@ -97,14 +110,29 @@ static int fill_params(const nmpc_config_t *c, nmpc::KParams *P)
     P->oEL = take(2 * nH);  // elastic variables of the HBM-resident kernel and their steps (one per inequality slot; only the pair / obstacle slots are used)
     P->oCKP = take((int64_t)((N - 1) / NMPC_CKPT_EVERY + 1) * (nx * nx + nx));      // saved cost-to-go of the backward sweep (partial re-factorisation)
     P->stride = o;
-    return 0;
+    nmpc::lds_kernel_workspace(*P, m, &P->oPACK, &P->oKT, &P->stride2);
+    {   // slack / dual arrays of the column kernel: pair, obstacle, control-bound (slacks + duals) and state-bound (duals) rows
+        const int64_t N1 = N + 1, NPd = m * (m - 1) / 2, MK = m * K;
+        const int64_t dual = 2 * N1 * NPd + 2 * N1 * MK + 4 * (int64_t)N * nu + 2 * N1 * P->nxb;
+        P->oDUAL = P->stride2;
+        P->stride2 += (dual + 15) / 16 * 16;
+    }
+    {   // cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep (partial re-factorisation after a rejected pivot): the column
+        // kernel stores its registers lane by lane, (3m + 1) x 64 doubles per slot; the element-per-lane kernel its [P | p] (smaller)
+        const int64_t slots = (N - 1) / NMPC_CKPT_EVERY + 1;
+        P->oCKPT = P->stride2;
+        P->stride2 += slots * (3 * m + 1) * 64;
+    }
+    {   // elastic variables t of the pair and obstacle rows (elastic phase only)
+        const int64_t el = (int64_t)(N + 1) * (m * (m - 1) / 2 + m * K);
+        P->oELAS = P->stride2;
+        P->stride2 += (el + 15) / 16 * 16;
+    }
 }
 
-int32_t nmpc_create(const nmpc_config_t *cfg, int32_t max_batch, nmpc_handle_t **out) { return nmpc_create_opts(cfg, max_batch, nullptr, out); }
-
-int32_t nmpc_create_opts(const nmpc_config_t *cfg, int32_t max_batch, const nmpc_options_t *opts, nmpc_handle_t **out)
+// the checks of nmpc_create_opts on a configuration and its options
+static int32_t config_check(const nmpc_config_t *cfg, const nmpc_options_t *opts)
 {
-    if (!cfg || !out || max_batch < 1) return NMPC_E_ARG;
     if (opts && (opts->kernel < 0 || opts->kernel > 5)) return NMPC_E_ARG;
     if (cfg->N < 2 || cfg->N > 4096 || cfg->n_obs < 0 || cfg->n_obs > NMPC_MAX_OBSTACLES) return NMPC_E_ARG;
     if (!(cfg->T > 0.0) || !(cfg->v_max > 0.0) || !(cfg->w_max > 0.0) || !(cfg->xy_max > 0.0) || !(cfg->th_max > 0.0)) return NMPC_E_ARG;
@@ -115,61 +143,109 @@ int32_t nmpc_create_opts(const nmpc_config_t *cfg, int32_t max_batch, const nmpc
     if (!(cfg->dmin >= 0.0) || (cfg->n_obs > 0 && (!(cfg->rob_dim >= 0.0) || !(cfg->margin >= 0.0)))) return NMPC_E_ARG;
     for (int o = 0; o < cfg->n_obs; o++) if (!(cfg->obs[3 * o + 2] >= 0.0)) return NMPC_E_ARG;
     if (cfg->pad_rows && !cfg->pair_rows) return NMPC_E_ARG;      // the padding rows only exist next to pair rows (C6:278)
-    if (!m_supported(cfg->m)) return NMPC_E_UNSUPPORTED;
+    return m_supported(cfg->m) ? NMPC_OK : NMPC_E_UNSUPPORTED;
+}
+
+// cus: compute units of the device
+static Selector selector_fill(const nmpc::KParams &P, int pin, int cus)
+{
+    Selector s;
+    const int m = P.m;
+    s.pin = pin;
+    s.base = (pin >= 1 && pin <= 2) ? pin : KERN_COL;
+    // horizons whose iterate does not fit the 160 KB of LDS of a CU run on the HBM-resident kernel (same algorithm, slower)
+    if (s.base == KERN_COL && nmpc::col_kernel_bytes(P, m, SHAPE_TP) > LDS_PER_CU) s.base = KERN_LDS;
+    const size_t lb = nmpc::col_kernel_bytes(P, m, SHAPE_LAT2), eb = nmpc::lds_kernel_bytes(P, m);
+    s.lat_fits = lb > 0 && lb <= LDS_PER_CU;
+    const int by_regs = m <= 6 ? 4 : 2, by_lds = s.lat_fits ? (int)(LDS_PER_CU / lb) : 0;
+    s.lat_slots = cus * (by_lds < by_regs ? by_lds : by_regs);
+    s.lat_slots4 = cus * (by_lds < 2 ? by_lds : 2);
+    if (s.base == KERN_LDS && eb > LDS_PER_CU) s.base = KERN_HBM;
+    s.lds_fits = eb <= LDS_PER_CU;
+    return s;
+}
+
+// The launch a solve of B instances makes: which kernel, in which shape, and the instantiation (the select_* function of that kernel).
+// solve_impl() launches by it; nmpc_query() and the nmpc_debug_variant* descriptors report it.  ordered: the call carries a dispatch-order
+// hint; needs_column: it passes an obstacle field or asks for the multipliers, which only the column kernel serves; field: the instantiation
+// reads the per-instance obstacle field.  false: the call is unsupported on this configuration (needs_column off the column kernel).
+static bool solve_plan(const nmpc::KParams &P, const Selector &s, int32_t B, bool ordered, bool needs_column, bool field, SolvePlan *pl)
+{
+    if (needs_column && s.base != KERN_COL) return false;      // horizon beyond the column kernel's LDS, or a pin to kernel 1 / 2
+    // Kernel.  The column-per-lane kernel (one wave per instance, two instances per SIMD up to six robots) is the
+    // throughput path.  A batch that cannot fill those slots is a latency problem instead (the launch lasts as long as its longest
+    // solve): there the element-per-lane kernel, one instance per SIMD and, for still smaller batches, 2-4 waves per instance, is
+    // faster.  Measured (solves/s, column | element), six robots: B=256 14.7 k | 16.7 k, 512 28.6 k | 31.0 k, 1024 54.0 k | 46.4 k,
+    // 2048 97 k | 89 k, 4096 164 k | 104 k, 8192 205 k | 131 k, 16384 251 k | 145 k; ten robots N=20: B=256 10.4 k | 11.9 k,
+    // 512 13.1 k | 13.4 k, 1024 25.5 k | 23.0 k, 2048 41.5 k | 25.5 k, 4096 59 k | 27 k; N=30: B=256 3.4 k | 3.8 k, 512 5.7 k | 4.7 k.
+    const int m = P.m;
+    int kern = s.base;
+    const bool own = s.base == KERN_COL && s.pin == 0;      // the column kernel, shape by batch size (pin 3: throughput shape always)
+    // With a dispatch-order hint (long solves first: the receding-horizon loop, nmpc_step_batch) the latency shape pays up to four rounds of
+    // instances — measured, six robots B=4096: sorted longest-first 15.5 ms against 18.4 ms in the throughput shape; warm closed loop 281 k
+    // against 248 k solves/s — because the order keeps a long solve from starting in the last round
+    if (ordered && own && s.lat_fits && m >= 4 && B <= 4 * s.lat_slots) kern = KERN_COL_LAT;
+    else if (s.base == KERN_COL && s.pin >= 4) kern = s.lat_fits ? KERN_COL_LAT : KERN_COL;      // pinned to the column kernel's latency shape
+    else if (own && s.lat_fits && m >= 4 && B <= 2 * s.lat_slots) {
+        // The column kernel's latency shape (two wavefronts per instance) where the launch lasts as long as its longest solve.  It holds
+        // lat_slots instances at once (4 per CU up to six robots: 256 VGPRs per wave; 2 per CU beyond; fewer when the LDS says so: the
+        // composite's 63 KB with its duals make it 2 per CU = 512).
+        // Measured, solves/s (throughput | latency shape): six robots B=512 34.6 k | 42.4 k, 1024 67 k | 83 k, 2048 122 k | 151 k, 4096 188 k | 174 k;
+        // composite 512 13.2 k | 18.6 k, 1024 25.4 k | 28.7 k, 2048 43.4 k | 41.2 k; ten robots N=20 512 13.5 k | 16.0 k, 1024 26.5 k | 31.5 k,
+        // 2048 49.5 k | 41.6 k; N=30 512 5.9 k | 6.9 k, 1024 11.2 k | 11.2 k.  Up to three robots a phase has no more than 64 items: nothing
+        // for a second wave to do (two robots 1024: 457 k | 462 k).
+        kern = KERN_COL_LAT;      // every measured crossover lies between two and four rounds of instances
+    } else if (own && !s.lat_fits && s.lds_fits && ((m >= 8 && B <= 256) || (m >= 5 && m <= 6 && B <= 512)))
+        kern = needs_column ? KERN_COL : KERN_LDS;      // a call that needs the column kernel keeps its throughput shape
+    pl->kernel = kern;
+    // latency shape: two wavefronts per instance, or four (pin 5; unpinned: five / six robots whose stage-parallel phases have more than 1000
+    // items (obstacle rows: (N-1) m K) while the batch fits twice the instances that shape holds at once (2 per CU))
+    const int64_t items = (int64_t)(P.N - 1) * m * P.K;
+    pl->shape = kern != KERN_COL_LAT ? SHAPE_TP
+                : s.pin == 4 ? SHAPE_LAT2
+                : (s.pin == 5 || (m >= 5 && m <= 6 && items > 1000 && B <= 2 * s.lat_slots4)) ? SHAPE_LAT4 : SHAPE_LAT2;
+    return kern == KERN_HBM   ? nmpc::select_solve(P, m, B, &pl->v)
+           : kern == KERN_LDS ? nmpc::select_solve_lds(P, m, B, &pl->v)
+                              : nmpc::select_solve_col(P, m, pl->shape, field, &pl->v);
+}
+
+int32_t nmpc_create(const nmpc_config_t *cfg, int32_t max_batch, nmpc_handle_t **out) { return nmpc_create_opts(cfg, max_batch, nullptr, out); }
+
+// the device side of nmpc_create_opts on the zeroed handle; on an error the caller destroys it
+static int32_t handle_init(nmpc_handle *h, const nmpc_config_t *cfg, int32_t max_batch, const nmpc_options_t *opts)
+{
+    if (hipGetDevice(&h->device) != hipSuccess) return NMPC_E_HIP;
+    h->cfg = *cfg;
+    fill_params(cfg, &h->P);
+    h->max_batch = max_batch;
+    int cus = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    h->sel = selector_fill(h->P, opts ? opts->kernel : 0, cus);
+    const int64_t per = h->sel.base == KERN_HBM ? h->P.stride : h->P.stride2;
+    h->ws_bytes = (int64_t)sizeof(double) * per * max_batch;
+    if (hipMalloc((void **)&h->ws, (size_t)h->ws_bytes) != hipSuccess) return NMPC_E_NOMEM;
+    if (hipMalloc((void **)&h->prof, (12 + 24 * 2048) * sizeof(long long)) != hipSuccess) return NMPC_E_NOMEM;
+    (void)hipMemset(h->prof, 0, (12 + 24 * 2048) * sizeof(long long));
+    if (hipMalloc((void **)&h->ord_chk, sizeof(int32_t) * ((size_t)max_batch + 1)) != hipSuccess) return NMPC_E_NOMEM;
+    (void)hipMemset(h->ord_chk, 0, sizeof(int32_t) * ((size_t)max_batch + 1));
+    if (hipMalloc((void **)&h->it_buf, sizeof(int32_t) * (size_t)max_batch) != hipSuccess) return NMPC_E_NOMEM;
+    if (hipMalloc((void **)&h->st_buf, sizeof(int32_t) * (size_t)max_batch) != hipSuccess) return NMPC_E_NOMEM;
+    h->P.trace_inst = opts ? opts->trace_instance : -1;
+    return NMPC_OK;
+}
+
+int32_t nmpc_create_opts(const nmpc_config_t *cfg, int32_t max_batch, const nmpc_options_t *opts, nmpc_handle_t **out)
+{
+    if (!cfg || !out || max_batch < 1) return NMPC_E_ARG;
+    int32_t rc = config_check(cfg, opts);
+    if (rc != NMPC_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return NMPC_E_HIP;   // fail loudly: no CPU path exists
     nmpc_handle *h = (nmpc_handle *)calloc(1, sizeof(nmpc_handle));
     if (!h) return NMPC_E_NOMEM;
-    if (hipGetDevice(&h->device) != hipSuccess) { free(h); return NMPC_E_HIP; }
-    h->cfg = *cfg;
-    fill_params(cfg, &h->P);
-    h->max_batch = max_batch;
-    const int pin = opts ? opts->kernel : 0;      // 0: chosen per batch size (kernel_for_batch)
-    h->kernel = pin ? (pin >= 4 ? 3 : pin) : 3;
-    h->col_lat = pin >= 4 ? 1 : (pin == 3 ? -1 : 0);      // 1: latency shape always, -1: throughput shape always, 0: by batch size
-    h->lat_waves = pin == 4 ? 2 : (pin == 5 ? 4 : 0);
-    // horizons whose iterate does not fit the 160 KB of LDS of a CU run on the HBM-resident kernel (same algorithm, slower)
-    if (h->kernel == 3 && nmpc::col_kernel_bytes(h->P, cfg->m, 0) > (size_t)160 * 1024) h->kernel = 2;
-    {
-        const size_t lb = nmpc::col_kernel_bytes(h->P, cfg->m, 1);
-        h->col_lat_ok = lb > 0 && lb <= (size_t)160 * 1024;
-        int cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        const int by_regs = cfg->m <= 6 ? 4 : 2, by_lds = h->col_lat_ok ? (int)((size_t)160 * 1024 / lb) : 0;
-        h->lat_slots = cus * (by_lds < by_regs ? by_lds : by_regs);
-        h->lat_slots4 = cus * (by_lds < 2 ? by_lds : 2);
-    }
-    if (h->kernel == 2 && nmpc::lds_kernel_bytes(h->P, cfg->m) > (size_t)160 * 1024) h->kernel = 1;
-    h->lat_ok = pin != 3 && pin < 4 && nmpc::lds_kernel_bytes(h->P, cfg->m) <= (size_t)160 * 1024;      // NMPC_KERNEL=3 pins the column kernel for every batch size
-    nmpc::lds_kernel_workspace(h->P, cfg->m, &h->P.oPACK, &h->P.oKT, &h->P.stride2);
-    {   // slack / dual arrays of the column kernel: pair, obstacle, control-bound (slacks + duals) and state-bound (duals) rows
-        const int64_t N = cfg->N, N1 = N + 1, m = cfg->m, NPd = m * (m - 1) / 2, MK = m * cfg->n_obs, NU = 2 * m, NXB = h->P.nxb;
-        const int64_t dual = 2 * N1 * NPd + 2 * N1 * MK + 4 * N * NU + 2 * N1 * NXB;
-        h->P.oDUAL = h->P.stride2;
-        h->P.stride2 += (dual + 15) / 16 * 16;
-    }
-    {   // cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep (partial re-factorisation after a rejected pivot): the column
-        // kernel stores its registers lane by lane, (3m + 1) x 64 doubles per slot; the element-per-lane kernel its [P | p] (smaller)
-        const int64_t slots = (cfg->N - 1) / NMPC_CKPT_EVERY + 1;
-        h->P.oCKPT = h->P.stride2;
-        h->P.stride2 += slots * (3 * cfg->m + 1) * 64;
-    }
-    {   // elastic variables t of the pair and obstacle rows (elastic phase only)
-        const int64_t N1 = cfg->N + 1, m = cfg->m, el = N1 * (m * (m - 1) / 2 + m * cfg->n_obs);
-        h->P.oELAS = h->P.stride2;
-        h->P.stride2 += (el + 15) / 16 * 16;
-    }
-    int64_t per = h->kernel == 1 ? h->P.stride : h->P.stride2;
-    h->ws_bytes = (int64_t)sizeof(double) * per * max_batch;
-    if (hipMalloc((void **)&h->ws, (size_t)h->ws_bytes) != hipSuccess) { free(h); return NMPC_E_NOMEM; }
-    if (hipMalloc((void **)&h->prof, (12 + 24 * 2048) * sizeof(long long)) != hipSuccess) { (void)hipFree(h->ws); free(h); return NMPC_E_NOMEM; }
-    (void)hipMemset(h->prof, 0, (12 + 24 * 2048) * sizeof(long long));
-    if (hipMalloc((void **)&h->ord_chk, sizeof(int32_t) * ((size_t)max_batch + 1)) != hipSuccess) { (void)hipFree(h->ws); (void)hipFree(h->prof); free(h); return NMPC_E_NOMEM; }
-    (void)hipMemset(h->ord_chk, 0, sizeof(int32_t) * ((size_t)max_batch + 1));
-    if (hipMalloc((void **)&h->it_buf, sizeof(int32_t) * (size_t)max_batch) != hipSuccess) { (void)hipFree(h->ws); (void)hipFree(h->prof); (void)hipFree(h->ord_chk); free(h); return NMPC_E_NOMEM; }
-    if (hipMalloc((void **)&h->st_buf, sizeof(int32_t) * (size_t)max_batch) != hipSuccess) { (void)hipFree(h->ws); (void)hipFree(h->prof); (void)hipFree(h->ord_chk); (void)hipFree(h->it_buf); free(h); return NMPC_E_NOMEM; }
-    h->P.trace_inst = opts ? opts->trace_instance : -1;
+    rc = handle_init(h, cfg, max_batch, opts);
+    if (rc != NMPC_OK) { nmpc_destroy(h); return rc; }
     *out = h;
     return NMPC_OK;
 }
@@ -188,70 +264,29 @@ int32_t nmpc_destroy(nmpc_handle_t *h)
 
 int64_t nmpc_workspace_bytes(const nmpc_handle_t *h) { return h ? h->ws_bytes : 0; }
 
-// which solve kernel a batch of B instances runs on: 1 HBM-resident, 2 element-per-lane (latency shapes), 3 column-per-lane (throughput)
-static int kernel_for_batch(const nmpc_handle_t *h, int32_t B, bool ordered = false)
+// The checks every entry point with an obstacle-field argument starts with.  CK_BOUNDED: B may not exceed max_batch; CK_OPT_FIELD: (NULL, 0) =
+// the handle's own field (the *_duals calls and nmpc_kkt_batch), else a per-instance field is required (obs may be NULL only for an empty
+// batch); CK_COLUMN: the call needs the column kernel.
+enum { CK_BOUNDED = 1, CK_OPT_FIELD = 2, CK_COLUMN = 4 };
+static int32_t call_check(const nmpc_handle_t *h, int32_t B, const double *obs, int32_t obs_stages, int ck)
 {
-    int kern = h->kernel;
-    // With a dispatch-order hint (long solves first: the receding-horizon loop, nmpc_step_batch) the latency shape pays up to four rounds of
-    // instances — measured, six robots B=4096: sorted longest-first 15.5 ms against 18.4 ms in the throughput shape; warm closed loop 281 k
-    // against 248 k solves/s — because the order keeps a long solve from starting in the last round
-    if (ordered && kern == 3 && h->col_lat == 0 && h->col_lat_ok && h->cfg.m >= 4 && B <= 4 * h->lat_slots) return 4;
-    if (kern == 3 && h->col_lat == 1) return h->col_lat_ok ? 4 : 3;      // pinned to the column kernel's latency shape
-    if (kern == 3 && h->col_lat == 0 && h->col_lat_ok && h->cfg.m >= 4) {
-        // The column kernel's latency shape (two wavefronts per instance) where the launch lasts as long as its longest solve.  It holds
-        // lat_slots instances at once (4 per CU up to six robots: 256 VGPRs per wave; 2 per CU beyond; fewer when the LDS says so: the
-        // composite's 63 KB with its duals make it 2 per CU = 512).
-        // Measured, solves/s (throughput | latency shape): six robots B=512 34.6 k | 42.4 k, 1024 67 k | 83 k, 2048 122 k | 151 k, 4096 188 k | 174 k;
-        // composite 512 13.2 k | 18.6 k, 1024 25.4 k | 28.7 k, 2048 43.4 k | 41.2 k; ten robots N=20 512 13.5 k | 16.0 k, 1024 26.5 k | 31.5 k,
-        // 2048 49.5 k | 41.6 k; N=30 512 5.9 k | 6.9 k, 1024 11.2 k | 11.2 k.  Up to three robots a phase has no more than 64 items: nothing
-        // for a second wave to do (two robots 1024: 457 k | 462 k).
-        if (B <= 2 * h->lat_slots) return 4;      // every measured crossover lies between two and four rounds of instances
-    }
-    if (kern == 3 && h->col_lat == 0 && !h->col_lat_ok && h->lat_ok && ((h->cfg.m >= 8 && B <= 256) || (h->cfg.m >= 5 && h->cfg.m <= 6 && B <= 512))) kern = 2;
-    return kern;
+    if (!h || B < 0 || ((ck & CK_BOUNDED) && B > h->max_batch)) return NMPC_E_ARG;
+    const bool own = (ck & CK_OPT_FIELD) && !obs && obs_stages == 0;
+    if (!own && (h->cfg.n_obs == 0 || (obs_stages != 1 && obs_stages != h->cfg.N) || (B > 0 && !obs))) return NMPC_E_ARG;
+    return ((ck & CK_COLUMN) && h->sel.base != KERN_COL) ? NMPC_E_UNSUPPORTED : NMPC_OK;
 }
 
-// the kernel of an *_obs call (column kernel only, h->kernel == 3): the plain call's choice, with the column kernel's throughput shape where that
-// would be the element-per-lane kernel
-static int kernel_for_batch_obs(const nmpc_handle_t *h, int32_t B, bool ordered = false)
+// the per-instance obstacle field [B][obs_stages][n_obs][3] of a call as the kernels read it
+static void set_field(nmpc::KParams *P, const nmpc_config_t &cfg, const double *obs, int32_t obs_stages)
 {
-    const int k = kernel_for_batch(h, B, ordered);
-    return k == 2 ? 3 : k;
-}
-
-// latency shape: two wavefronts per instance (1), or four (2) for five / six robots whose stage-parallel phases have more than 1000 items
-// (obstacle rows: (N-1) m K) while the batch fits twice the instances that shape holds at once (2 per CU)
-static int lat_waves_shape(const nmpc_handle_t *h, int32_t B)
-{
-    if (h->lat_waves == 2 || h->lat_waves == 4) return h->lat_waves == 4 ? 2 : 1;
-    const int64_t items = (int64_t)(h->cfg.N - 1) * h->cfg.m * h->cfg.n_obs;
-    return (h->cfg.m >= 5 && h->cfg.m <= 6 && items > 1000 && B <= 2 * h->lat_slots4) ? 2 : 1;
-}
-
-// The launch a solve of B instances makes: kern as kernel_for_batch*() (4: the column kernel's latency shape), shape as launch_solve_col*
-// take it, and the instantiation the launcher of that kernel selects.  solve_impl() launches by it, nmpc_debug_variant() reports it.
-// col: the call needs the column kernel (an obstacle field, or the multipliers: h->kernel == 3 is the caller's check)
-static bool launch_choice(const nmpc_handle_t *h, int32_t B, bool ordered, bool obs, int *kern, int *shape, nmpc::SolveVariant *v, bool col = false)
-{
-    *kern = (obs || col) ? kernel_for_batch_obs(h, B, ordered) : kernel_for_batch(h, B, ordered);
-    *shape = *kern == 4 ? lat_waves_shape(h, B) : 0;
-    if (obs) return nmpc::select_solve_col(h->P, h->cfg.m, *shape, true, v);
-    return *kern == 1   ? nmpc::select_solve(h->P, h->cfg.m, B, v)
-           : *kern == 2 ? nmpc::select_solve_lds(h->P, h->cfg.m, B, v)
-                        : nmpc::select_solve_col(h->P, h->cfg.m, *shape, false, v);
-}
-
-// the per-instance obstacle field of the *_obs entry points: NMPC_OK, or the error of a bad field (obs may be NULL only for an empty batch)
-static int32_t obs_field_check(const nmpc_handle_t *h, int32_t B, const double *obs, int32_t obs_stages)
-{
-    if (!h) return NMPC_E_ARG;
-    if (h->cfg.n_obs == 0 || (obs_stages != 1 && obs_stages != h->cfg.N) || (B > 0 && !obs)) return NMPC_E_ARG;
-    return NMPC_OK;
+    P->ofield.ptr = obs;
+    P->ofield.istride = obs_stages * cfg.n_obs * 3;
+    P->ofield.sstride = obs_stages == 1 ? 0 : cfg.n_obs * 3;
 }
 
 static bool wants_duals(const nmpc_duals_t *d) { return d && (d->lam_g || d->lam_x || d->lam_p); }
 
-// obs != NULL: the obstacle field of the instances, [B][obs_stages][n_obs][3] (checked by obs_field_check), read by the column kernel's
+// obs != NULL: the obstacle field of the instances, [B][obs_stages][n_obs][3] (checked by call_check), read by the column kernel's
 // per-instance field instantiations; handles that run on kernel 1 or 2 have none.  duals: the multiplier outputs of the *_duals entry points,
 // written by the column kernel's epilogue (nullptr, or all members nullptr: the plain call)
 static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
@@ -260,7 +295,8 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
     const bool du = wants_duals(duals);
-    if ((obs || du) && h->kernel != 3) return NMPC_E_UNSUPPORTED;      // horizon beyond the column kernel's LDS, or a pin to kernel 1 / 2
+    SolvePlan pl;
+    if (!solve_plan(h->P, h->sel, B, order != nullptr, obs || du, obs != nullptr, &pl)) return NMPC_E_UNSUPPORTED;
     if (B == 0) return NMPC_OK;      /* empty batch: nothing to read or write, pointers may be null */
     if (!p || !w0 || !w_out) return NMPC_E_ARG;
     DeviceScope dev(h->device);
@@ -268,29 +304,13 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
     nmpc::KParams P = h->P;
     P.order = order;
     P.order_bad = h->ord_chk + B;
-    if (obs) {
-        P.ofield.ptr = obs;
-        P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
-        P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
-    }
+    if (obs) set_field(&P, h->cfg, obs, obs_stages);
     if (du) { P.lam_g = duals->lam_g; P.lam_x = duals->lam_x; P.lam_p = duals->lam_p; }
     if (order && nmpc::launch_order_check(B, order, h->ord_chk, h->ord_chk + B, (hipStream_t)stream) != hipSuccess) return NMPC_E_HIP;
-    // Launch shape.  The column-per-lane kernel (one wave per instance, two instances per SIMD up to six robots) is the
-    // throughput path.  A batch that cannot fill those slots is a latency problem instead (the launch lasts as long as its longest
-    // solve): there the element-per-lane kernel, one instance per SIMD and, for still smaller batches, 2-4 waves per instance, is
-    // faster.  Measured (solves/s, column | element), six robots: B=256 14.7 k | 16.7 k, 512 28.6 k | 31.0 k, 1024 54.0 k | 46.4 k,
-    // 2048 97 k | 89 k, 4096 164 k | 104 k, 8192 205 k | 131 k, 16384 251 k | 145 k; ten robots N=20: B=256 10.4 k | 11.9 k,
-    // 512 13.1 k | 13.4 k, 1024 25.5 k | 23.0 k, 2048 41.5 k | 25.5 k, 4096 59 k | 27 k; N=30: B=256 3.4 k | 3.8 k, 512 5.7 k | 4.7 k.
-    int kern, shape;
-    nmpc::SolveVariant var;
-    if (!launch_choice(h, B, order != nullptr, obs != nullptr, &kern, &shape, &var, du)) return NMPC_E_HIP;
-    if (obs) {
-        hipError_t e = nmpc::launch_solve_col_obs(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, shape);
-        return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
-    }
-    hipError_t e = (kern == 1)   ? nmpc::launch_solve(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, (hipStream_t)stream)
-                   : (kern == 2) ? nmpc::launch_solve_lds(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream)
-                                 : nmpc::launch_solve_col(P, h->cfg.m, B, p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, (hipStream_t)stream, shape);
+    const nmpc::SolveArgs a{p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof};
+    hipError_t e = pl.v.kernel == KERN_HBM   ? nmpc::launch_solve(P, pl.v, B, a, (hipStream_t)stream)
+                   : pl.v.kernel == KERN_LDS ? nmpc::launch_solve_lds(P, pl.v, B, a, (hipStream_t)stream)
+                                             : nmpc::launch_solve_col(P, pl.v, B, a, (hipStream_t)stream);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 
@@ -310,7 +330,7 @@ static int32_t step_impl(nmpc_handle_t *h, int32_t B, double *p, double *w, doub
                          int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0, const nmpc_duals_t *duals = nullptr)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    if ((obs || wants_duals(duals)) && h->kernel != 3) return NMPC_E_UNSUPPORTED;
+    if ((obs || wants_duals(duals)) && h->sel.base != KERN_COL) return NMPC_E_UNSUPPORTED;
     if (B == 0) return NMPC_OK;
     if (!p || !w || !w_sol || w == w_sol) return NMPC_E_ARG;
     int32_t *it = iters ? iters : h->it_buf;
@@ -338,21 +358,15 @@ int32_t nmpc_step_batch(nmpc_handle_t *h, int32_t B, double *p, double *w, doubl
 int32_t nmpc_solve_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
                              double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order, void *stream)
 {
-    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    int32_t rc = obs_field_check(h, B, obs, obs_stages);
-    if (rc != NMPC_OK) return rc;
-    if (B == 0) return h->kernel == 3 ? NMPC_OK : NMPC_E_UNSUPPORTED;
-    return solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages);
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_COLUMN);
+    return rc != NMPC_OK ? rc : solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages);
 }
 
 int32_t nmpc_step_batch_obs(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *obs, int32_t obs_stages, double *obj,
                             int32_t *status, int32_t *iters, double *kkt, int32_t *order, void *stream)
 {
-    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    int32_t rc = obs_field_check(h, B, obs, obs_stages);
-    if (rc != NMPC_OK) return rc;
-    if (B == 0) return h->kernel == 3 ? NMPC_OK : NMPC_E_UNSUPPORTED;
-    return step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages);
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_COLUMN);
+    return rc != NMPC_OK ? rc : step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages);
 }
 
 int32_t nmpc_eval_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *w, double *f, double *g, void *stream)
@@ -369,64 +383,43 @@ int32_t nmpc_eval_batch(nmpc_handle_t *h, int32_t B, const double *p, const doub
 int32_t nmpc_eval_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *obs, int32_t obs_stages, double *f, double *g,
                             void *stream)
 {
-    if (!h || B < 0) return NMPC_E_ARG;
-    int32_t rc = obs_field_check(h, B, obs, obs_stages);
+    const int32_t rc = call_check(h, B, obs, obs_stages, 0);
     if (rc != NMPC_OK) return rc;
     if (B == 0) return NMPC_OK;
     if (!p || !w) return NMPC_E_ARG;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
     nmpc::KParams P = h->P;
-    P.ofield.ptr = obs;
-    P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
-    P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
+    set_field(&P, h->cfg, obs, obs_stages);
     hipError_t e = nmpc::launch_eval(P, h->cfg.m, B, p, w, f, g, (hipStream_t)stream, true);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
-}
-
-// the obstacle arguments of the *_duals calls and nmpc_kkt_batch: (NULL, 0) = the handle's own field, else those of the *_obs calls
-static int32_t opt_field_check(const nmpc_handle_t *h, int32_t B, const double *obs, int32_t obs_stages)
-{
-    if (!h) return NMPC_E_ARG;
-    return (!obs && obs_stages == 0) ? NMPC_OK : obs_field_check(h, B, obs, obs_stages);
 }
 
 int32_t nmpc_solve_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
                                double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order, const nmpc_duals_t *duals, void *stream)
 {
-    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    int32_t rc = opt_field_check(h, B, obs, obs_stages);
-    if (rc != NMPC_OK) return rc;
-    if (h->kernel != 3) return NMPC_E_UNSUPPORTED;
-    return solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    return rc != NMPC_OK ? rc : solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
 }
 
 int32_t nmpc_step_batch_duals(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *obs, int32_t obs_stages, double *obj,
                               int32_t *status, int32_t *iters, double *kkt, int32_t *order, const nmpc_duals_t *duals, void *stream)
 {
-    if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    int32_t rc = opt_field_check(h, B, obs, obs_stages);
-    if (rc != NMPC_OK) return rc;
-    if (h->kernel != 3) return NMPC_E_UNSUPPORTED;
-    return step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    return rc != NMPC_OK ? rc : step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
 }
 
 int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
                        const double *lam_x, double *res, double *grad_lag, void *stream)
 {
-    if (!h || B < 0) return NMPC_E_ARG;
-    int32_t rc = opt_field_check(h, B, obs, obs_stages);
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_OPT_FIELD);
     if (rc != NMPC_OK) return rc;
     if (B == 0) return NMPC_OK;
     if (!p || !w || !lam_g || !lam_x || !res) return NMPC_E_ARG;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
     nmpc::KParams P = h->P;
-    if (obs) {
-        P.ofield.ptr = obs;
-        P.ofield.istride = obs_stages * h->cfg.n_obs * 3;
-        P.ofield.sstride = obs_stages == 1 ? 0 : h->cfg.n_obs * 3;
-    }
+    if (obs) set_field(&P, h->cfg, obs, obs_stages);
     hipError_t e = nmpc::launch_kkt(P, h->cfg.m, B, p, w, lam_g, lam_x, res, grad_lag, (hipStream_t)stream, obs != nullptr);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
@@ -456,15 +449,15 @@ int32_t nmpc_odometry_batch(int64_t n, const double *odom, const double *init, d
 int64_t nmpc_query(const nmpc_handle_t *h, int32_t what, int64_t arg)
 {
     if (!h) return NMPC_E_ARG;
+    SolvePlan pl;
     switch (what) {
-    case NMPC_QUERY_KERNEL_FOR_BATCH: return (arg < 0 || arg > h->max_batch) ? NMPC_E_ARG : kernel_for_batch(h, (int32_t)arg);
-    case NMPC_QUERY_KERNEL_FOR_ORDERED_BATCH: return (arg < 0 || arg > h->max_batch) ? NMPC_E_ARG : kernel_for_batch(h, (int32_t)arg, true);
+    case NMPC_QUERY_KERNEL_FOR_BATCH:
+    case NMPC_QUERY_KERNEL_FOR_ORDERED_BATCH:
+    case NMPC_QUERY_LDS_BYTES:
+        if (arg < 0 || arg > h->max_batch || !solve_plan(h->P, h->sel, (int32_t)arg, what == NMPC_QUERY_KERNEL_FOR_ORDERED_BATCH, false, false, &pl)) return NMPC_E_ARG;
+        if (what != NMPC_QUERY_LDS_BYTES) return pl.kernel;
+        return pl.kernel == KERN_LDS ? (int64_t)nmpc::lds_kernel_bytes(h->P, h->cfg.m) : (int64_t)pl.v.lds;      // kernel 2: its throughput shape's, whatever B
     case NMPC_QUERY_WORKSPACE_BYTES: return h->ws_bytes;
-    case NMPC_QUERY_LDS_BYTES: {
-        if (arg < 0 || arg > h->max_batch) return NMPC_E_ARG;
-        const int k = kernel_for_batch(h, (int32_t)arg);
-        return (k == 3 || k == 4) ? (int64_t)nmpc::col_kernel_bytes(h->P, h->cfg.m, k == 4) : (k == 2 ? (int64_t)nmpc::lds_kernel_bytes(h->P, h->cfg.m) : 0);
-    }
     case NMPC_QUERY_MAX_BATCH: return h->max_batch;
     default: return NMPC_E_ARG;
     }
@@ -500,8 +493,8 @@ int32_t nmpc_debug_trace2(nmpc_handle_t *h, double *out, int32_t rows)
 int64_t nmpc_debug_workspace(nmpc_handle_t *h, int32_t inst, double *out, int64_t cap, int64_t *offs)
 {
     if (!h) return NMPC_E_ARG;
-    int64_t per = h->kernel == 1 ? h->P.stride : h->P.stride2;
-    if (offs) { offs[0] = h->kernel; offs[1] = h->P.oKG; offs[2] = h->P.oKFF; offs[3] = h->P.oPACK; offs[4] = h->P.oKT; }
+    int64_t per = h->sel.base == KERN_HBM ? h->P.stride : h->P.stride2;
+    if (offs) { offs[0] = h->sel.base; offs[1] = h->P.oKG; offs[2] = h->P.oKFF; offs[3] = h->P.oPACK; offs[4] = h->P.oKT; }
     if (!out) return per;
     if (cap < per || inst < 0 || inst >= h->max_batch) return NMPC_E_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return NMPC_E_HIP;
@@ -509,17 +502,36 @@ int64_t nmpc_debug_workspace(nmpc_handle_t *h, int32_t inst, double *out, int64_
     return per;
 }
 
+/* the descriptor of a plan, with the codes of the call it describes */
+static int32_t describe(const nmpc_config_t &cfg, const nmpc::KParams &P, const Selector &sel, int32_t B, int32_t ordered, int32_t obs_field,
+                        nmpc_debug_variant_t *out, int32_t *kernel)
+{
+    if (obs_field && cfg.n_obs == 0) return NMPC_E_ARG;      // as call_check()
+    SolvePlan pl;
+    if (!solve_plan(P, sel, B, ordered != 0, obs_field != 0, obs_field != 0, &pl)) return NMPC_E_UNSUPPORTED;
+    const nmpc::SolveVariant &v = pl.v;
+    out->kernel = v.kernel; out->m = v.m; out->thb = v.thb; out->flags = v.flags; out->threads = v.threads; out->lds_bytes = (int64_t)v.lds;
+    if (kernel) *kernel = pl.kernel;
+    return NMPC_OK;
+}
+
 /* the instantiation a solve of B instances on this handle would launch; no launch is made */
 int32_t nmpc_debug_variant(const nmpc_handle_t *h, int32_t B, int32_t ordered, int32_t obs_field, nmpc_debug_variant_t *out)
 {
     if (!h || !out || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    if (obs_field && h->cfg.n_obs == 0) return NMPC_E_ARG;      // as obs_field_check()
-    if (obs_field && h->kernel != 3) return NMPC_E_UNSUPPORTED;
-    int kern, shape;
-    nmpc::SolveVariant v;
-    if (!launch_choice(h, B, ordered != 0, obs_field != 0, &kern, &shape, &v)) return NMPC_E_UNSUPPORTED;
-    out->kernel = v.kernel; out->m = v.m; out->thb = v.thb; out->flags = v.flags; out->threads = v.threads; out->lds_bytes = (int64_t)v.lds;
-    return NMPC_OK;
+    return describe(h->cfg, h->P, h->sel, B, ordered, obs_field, out, nullptr);
+}
+
+/* the same for the handle nmpc_create_opts(cfg, >= B, opts) makes on a device with that many compute units; needs neither */
+int32_t nmpc_debug_variant_of_config(const nmpc_config_t *cfg, const nmpc_options_t *opts, int32_t compute_units, int32_t B, int32_t ordered,
+                                     int32_t obs_field, nmpc_debug_variant_t *out, int32_t *kernel)
+{
+    if (!cfg || !out || compute_units < 1 || B < 0) return NMPC_E_ARG;
+    const int32_t rc = config_check(cfg, opts);
+    if (rc != NMPC_OK) return rc;
+    nmpc::KParams P;
+    fill_params(cfg, &P);
+    return describe(*cfg, P, selector_fill(P, opts ? opts->kernel : 0, compute_units), B, ordered, obs_field, out, kernel);
 }
 
 #ifndef NMPC_SRC_HASH

@@ -3,12 +3,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/nmpc.h"
 
 // shared with the CPU oracles: NMPC_SHIFT_ESCALATION, NMPC_COLD_RETRY_ITERS, NMPC_COLD_RETRIES, NMPC_X0_TOL
 #include "../../include/nmpc_constants.h"
 
 namespace nmpc {
+
+// f(std::integral_constant<int, M>{}) for the team size m = M in 1 .. NMPC_MAX_ROBOTS (every one is instantiated), `none` for any other m
+template <int M = 1, class R, class F> R for_team_size(int m, R none, F &&f)
+{
+    if constexpr (M > NMPC_MAX_ROBOTS) return none;
+    else return m == M ? f(std::integral_constant<int, M>{}) : for_team_size<M + 1>(m, none, f);
+}
 
 // Passed by value to every kernel (lands in SGPRs / the kernarg segment).
 struct KParams {
@@ -39,27 +48,36 @@ struct KParams {
     int32_t oX, oU, oLAM, oS, oZ, oDX, oDU, oLAMN, oDS, oDZ, oSN, oCS, oC, oH, oGX, oHUU, oGU, oHVT, oHTT, oKG, oKFF, oCKP, oEL;      // oCKP: the HBM-resident kernel's saved cost-to-go, [(N-1)/NMPC_CKPT_EVERY + 1][nx * nx + nx]; oEL: its elastic variables, one per inequality slot
 };
 
+// The solve kernels by the code nmpc_options_t.kernel pins and NMPC_QUERY_KERNEL_FOR_BATCH answers (include/nmpc.h), and the shapes of the
+// column kernel: one, two or four wavefronts per instance.  KERN_COL_LAT is the column kernel in one of its two latency shapes.
+enum { KERN_HBM = 1, KERN_LDS = 2, KERN_COL = 3, KERN_COL_LAT = 4 };
+enum { SHAPE_TP = 0, SHAPE_LAT2 = 1, SHAPE_LAT4 = 2 };
+
 // The instantiation one launch runs: the template arguments of solve_kernel<M, TPB> (kernel 1), solve_lds_kernel<M, THB, TPB> (2) or
-// solve_col_kernel<M, THB, DL, TPB> (3), and its dynamic LDS.  Filled by the select_* function of each kernel, which its launcher calls too.
+// solve_col_kernel<M, THB, DL, TPB> (3), and its dynamic LDS.  Filled by the select_* function of each kernel; its launcher launches exactly
+// this instantiation (hipErrorInvalidValue where it does not exist) and selects nothing itself.
 struct SolveVariant {
-    int kernel, m, thb, flags, threads;      // thb: 0 for kernel 1 (no such template argument); flags: DL of the column kernel, else 0
+    int kernel, m, thb, flags, threads;      // kernel: KERN_HBM / KERN_LDS / KERN_COL; thb: 0 for kernel 1 (no such template argument); flags: DL of the column kernel, else 0
     size_t lds;
 };
 // false: team size not instantiated
 bool select_solve(const KParams &P, int m, int B, SolveVariant *v);
 bool select_solve_lds(const KParams &P, int m, int B, SolveVariant *v);
-bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVariant *v);      // shape and ofield as launch_solve_col / launch_solve_col_obs
+bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVariant *v);      // shape: SHAPE_*; ofield: the per-instance obstacle field P.ofield
 
-hipError_t launch_solve(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                        int32_t *iters, double *kkt, double *ws, hipStream_t st);
-hipError_t launch_solve_lds(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                            int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st);
-size_t lds_kernel_bytes(const KParams &P, int m);
-hipError_t launch_solve_col(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                            int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape);      // shape: 0 throughput, 1 latency (two wavefronts per instance)
-hipError_t launch_solve_col_obs(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                                int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape);      // launch_solve_col with the obstacle field P.ofield
-size_t col_kernel_bytes(const KParams &P, int m, int shape);
+// device pointers of one solve call: inputs, outputs (each of obj .. kkt may be nullptr), the handle's workspace and profile counters
+struct SolveArgs {
+    const double *p, *w0;
+    double *w_out, *obj;
+    int32_t *status, *iters;
+    double *kkt, *ws;
+    long long *prof;
+};
+hipError_t launch_solve(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st);
+hipError_t launch_solve_lds(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st);
+hipError_t launch_solve_col(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st);
+size_t lds_kernel_bytes(const KParams &P, int m);                 // the element-per-lane kernel's throughput shape
+size_t col_kernel_bytes(const KParams &P, int m, int shape);      // = select_solve_col(..).lds
 void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride);
 hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
 // KKT residuals of (w, lam_g, lam_x): res [B][6] = (stat, eq, ineq, bnd, compl, sign), grad_lag [B][nvar] or nullptr (include/nmpc.h, nmpc_kkt_batch)

@@ -1062,11 +1062,11 @@ __global__ __launch_bounds__(256) void shift_kernel(const KParams P, int B, cons
 // host-side launchers (called from nmpc_api.cpp)
 // workgroup size of the HBM-resident kernel: its only choice (no dynamic LDS, no heading-bound template argument)
 template <int M_> static constexpr int solve_threads() { return (M_ <= 6) ? 64 : 128; }
-template <int M_> static hipError_t launch_solve_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
-                                                   int32_t *status, int32_t *iters, double *kkt, double *ws, hipStream_t st)
+template <int M_> static hipError_t launch_solve_m(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
     constexpr int TPB = solve_threads<M_>();
-    hipLaunchKernelGGL((solve_kernel<M_, TPB>), dim3(B), dim3(TPB), 0, st, P, p, w0, w_out, obj, status, iters, kkt, ws);
+    if (v.kernel != KERN_HBM || v.threads != TPB) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((solve_kernel<M_, TPB>), dim3(B), dim3(TPB), 0, st, P, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws);
     return hipGetLastError();
 }
 template <int M_> static hipError_t launch_eval_m(const KParams &P, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
@@ -1181,56 +1181,26 @@ hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hi
     return hipGetLastError();
 }
 
-#define NMPC_DISPATCH(M, CALL)                                                                                                    \
-    switch (M) {                                                                                                                  \
-    case 1: return CALL(1);                                                                                                       \
-    case 2: return CALL(2);                                                                                                       \
-    case 3: return CALL(3);                                                                                                       \
-    case 4: return CALL(4);                                                                                                       \
-    case 5: return CALL(5);                                                                                                       \
-    case 6: return CALL(6);                                                                                                       \
-    case 7: return CALL(7);                                                                                                       \
-    case 8: return CALL(8);                                                                                                       \
-    case 9: return CALL(9);                                                                                                       \
-    case 10: return CALL(10);                                                                                                     \
-    default: return hipErrorInvalidValue;                                                                                         \
-    }
-
-hipError_t launch_solve(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                        int32_t *iters, double *kkt, double *ws, hipStream_t st)
+hipError_t launch_solve(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
-#define C_(M) launch_solve_m<M>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, st)
-    NMPC_DISPATCH(m, C_)
-#undef C_
+    return for_team_size(v.m, hipErrorInvalidValue, [&](auto M) { return launch_solve_m<decltype(M)::value>(P, v, B, a, st); });
 }
 bool select_solve(const KParams &, int m, int, SolveVariant *v)
 {
-#define C_(M) (*v = SolveVariant{1, M, 0, 0, solve_threads<M>(), 0}, true)
-    switch (m) {
-    case 1: return C_(1); case 2: return C_(2); case 3: return C_(3); case 4: return C_(4); case 5: return C_(5);
-    case 6: return C_(6); case 7: return C_(7); case 8: return C_(8); case 9: return C_(9); case 10: return C_(10);
-    default: return false;
-    }
-#undef C_
+    return for_team_size(m, false, [&](auto M) { return *v = SolveVariant{KERN_HBM, decltype(M)::value, 0, 0, solve_threads<decltype(M)::value>(), 0}, true; });
 }
 hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
 {
-#define C_(M) launch_eval_m<M>(P, B, p, w, f, g, st, ofield)
-    NMPC_DISPATCH(m, C_)
-#undef C_
+    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_eval_m<decltype(M)::value>(P, B, p, w, f, g, st, ofield); });
 }
 hipError_t launch_kkt(const KParams &P, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
                       hipStream_t st, bool ofield)
 {
-#define C_(M) launch_kkt_m<M>(P, B, p, w, lam_g, lam_x, res, grad_lag, st, ofield)
-    NMPC_DISPATCH(m, C_)
-#undef C_
+    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_kkt_m<decltype(M)::value>(P, B, p, w, lam_g, lam_x, res, grad_lag, st, ofield); });
 }
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st)
 {
-#define C_(M) launch_shift_m<M>(P, B, p, w_in, w_next, x0n, x0_stride, keep_status, st)
-    NMPC_DISPATCH(m, C_)
-#undef C_
+    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_shift_m<decltype(M)::value>(P, B, p, w_in, w_next, x0n, x0_stride, keep_status, st); });
 }
 
 }  // namespace nmpc

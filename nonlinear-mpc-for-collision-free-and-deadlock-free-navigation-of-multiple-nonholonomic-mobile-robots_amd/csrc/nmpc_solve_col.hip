@@ -1744,7 +1744,7 @@ template <int M_, int OBS> struct ColInst {
     // obstacles: composite B=1024 28.7 k -> 33.5 k solves/s; six robots without obstacles B=512 42.3 k -> 43.4 k) and the build time counts
     static constexpr int TPB4 = (M_ == 5 || M_ == 6) ? 256 : 128;
 };
-// the instantiation a launch in the given shape runs (shape: 0 throughput, 1 / 2 latency with two / four wavefronts per instance)
+// the instantiation a launch in the given shape runs (shape: SHAPE_TP throughput, SHAPE_LAT2 / SHAPE_LAT4 latency with two / four wavefronts per instance)
 template <int M_, int THB, int OBS> static SolveVariant select3_mt(const KParams &P, int shape)
 {
     using I = ColInst<M_, OBS>;
@@ -1753,19 +1753,17 @@ template <int M_, int THB, int OBS> static SolveVariant select3_mt(const KParams
     const int fl = (!lat && dl) ? col_factor_mode<M_, THB>(P) : 0;
     const size_t lds = col_lds_bytes<M_, THB>(P, dl, fl);
     if (shape == 2 && I::TPB4 == 128) shape = 1;
-    if (shape == 2) return SolveVariant{3, M_, THB, I::DLlat | I::OB, I::TPB4, lds};
-    if (lat) return SolveVariant{3, M_, THB, I::DLlat | I::OB, 128, lds};
-    if (fl) return SolveVariant{3, M_, THB, I::DLmax * I::FLM | I::OB, 64, lds};
-    return SolveVariant{3, M_, THB, (dl ? I::DLmax : 0) | I::OB, 64, lds};
+    if (shape == 2) return SolveVariant{KERN_COL, M_, THB, I::DLlat | I::OB, I::TPB4, lds};
+    if (lat) return SolveVariant{KERN_COL, M_, THB, I::DLlat | I::OB, 128, lds};
+    if (fl) return SolveVariant{KERN_COL, M_, THB, I::DLmax * I::FLM | I::OB, 64, lds};
+    return SolveVariant{KERN_COL, M_, THB, (dl ? I::DLmax : 0) | I::OB, 64, lds};
 }
-template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
-                                                        int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape)
+// launches the instantiation whose template arguments are v's
+template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
     using I = ColInst<M_, OBS>;
-    const SolveVariant v = select3_mt<M_, THB, OBS>(P, shape);
     const size_t lds = v.lds;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    // the instantiation whose template arguments are v's
     auto kern = (v.threads == I::TPB4 && v.flags == (I::DLlat | I::OB)) ? solve_col_kernel<M_, THB, I::DLlat | I::OB, I::TPB4>
                 : (v.threads == 128 && v.flags == (I::DLlat | I::OB)) ? solve_col_kernel<M_, THB, I::DLlat | I::OB, 128>
                 : (v.threads == 64 && v.flags == (I::DLmax * I::FLM | I::OB)) ? solve_col_kernel<M_, THB, I::DLmax * I::FLM | I::OB, 64>
@@ -1776,134 +1774,64 @@ template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(v.threads), lds, st, P, p, w0, w_out, obj, status, iters, kkt, ws, prof);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(v.threads), lds, st, P, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws, a.prof);
     return hipGetLastError();
 }
-template <int M_, int OBS> static hipError_t launch3_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                                                       int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st, int shape)
+
+// One compile unit of the kernel: the team sizes LO..HI with (OBS = 1) or without the per-instance obstacle field.  The ten team sizes take
+// ~350 s per field flag in one translation unit, so build.py compiles this source once per unit (-DNMPC_COL_UNIT=LO,HI,OBS: one object each,
+// spread over the cores); the unit built with -DNMPC_COL_ENTRY carries the host entry points below as well.  Without NMPC_COL_UNIT (variant
+// builds, NMPC_COL_ONLY_M) everything is in this one object.
+template <int LO, int HI, int OBS> hipError_t launch_col_unit(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
-    return P.thb ? launch3_mt<M_, 1, OBS>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape)
-                 : launch3_mt<M_, 0, OBS>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
+    return for_team_size(v.m, hipErrorInvalidValue, [&](auto M) {
+        constexpr int M_ = decltype(M)::value;
+        if constexpr (M_ >= LO && M_ <= HI) return v.thb ? launch3_mt<M_, 1, OBS>(P, v, B, a, st) : launch3_mt<M_, 0, OBS>(P, v, B, a, st);
+        else return hipErrorInvalidValue;
+    });
 }
 
-// The team sizes are instantiated in up to six objects so that the build spreads over the cores (one hipcc -c per part, see build.py;
-// the ten team sizes take ~350 s in one translation unit): NMPC_COL_PART 0 = everything here (variants, NMPC_COL_ONLY_M), 1 = the entry
-// points below plus 1..5 robots, 2 = 6..8 robots, 3 = 9..10 robots; 4, 5, 6 = the same team sizes for the per-instance obstacle field.
-#ifndef NMPC_COL_PART
-#define NMPC_COL_PART 0
-#endif
-#define COL_ARGS_DECL const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status, int32_t *iters, \
-                      double *kkt, double *ws, long long *prof, hipStream_t st, int shape
-#define COL_ARGS P, m, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape
-#define COL_CASE(M, OBS) case M: return launch3_m<M, OBS>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st, shape);
-#if NMPC_COL_PART == 2
-hipError_t launch_solve_col_part2(COL_ARGS_DECL)
-{
-    switch (m) {
-        COL_CASE(6, 0) COL_CASE(7, 0) COL_CASE(8, 0)
-    default: return hipErrorInvalidValue;
-    }
-}
-#elif NMPC_COL_PART == 3
-hipError_t launch_solve_col_part3(COL_ARGS_DECL)
-{
-    switch (m) {
-        COL_CASE(9, 0) COL_CASE(10, 0)
-    default: return hipErrorInvalidValue;
-    }
-}
-#elif NMPC_COL_PART == 4
-hipError_t launch_solve_col_obs_part1(COL_ARGS_DECL)
-{
-    switch (m) {
-        COL_CASE(1, 1) COL_CASE(2, 1) COL_CASE(3, 1) COL_CASE(4, 1) COL_CASE(5, 1)
-    default: return hipErrorInvalidValue;
-    }
-}
-#elif NMPC_COL_PART == 5
-hipError_t launch_solve_col_obs_part2(COL_ARGS_DECL)
-{
-    switch (m) {
-        COL_CASE(6, 1) COL_CASE(7, 1) COL_CASE(8, 1)
-    default: return hipErrorInvalidValue;
-    }
-}
-#elif NMPC_COL_PART == 6
-hipError_t launch_solve_col_obs_part3(COL_ARGS_DECL)
-{
-    switch (m) {
-        COL_CASE(9, 1) COL_CASE(10, 1)
-    default: return hipErrorInvalidValue;
-    }
-}
-#else
-#if NMPC_COL_PART == 1
-hipError_t launch_solve_col_part2(COL_ARGS_DECL);
-hipError_t launch_solve_col_part3(COL_ARGS_DECL);
-hipError_t launch_solve_col_obs_part1(COL_ARGS_DECL);
-hipError_t launch_solve_col_obs_part2(COL_ARGS_DECL);
-hipError_t launch_solve_col_obs_part3(COL_ARGS_DECL);
-#endif
-// shape: 0 = throughput (one wavefront per instance), 1 / 2 = latency (two / four wavefronts per instance, see the kernel)
-hipError_t launch_solve_col(COL_ARGS_DECL)
-{
-    switch (m) {
+#if !defined(NMPC_COL_UNIT) || defined(NMPC_COL_ENTRY)
+// the units: the table COL_UNITS of build.py
 #ifdef NMPC_COL_ONLY_M
-        COL_CASE(NMPC_COL_ONLY_M, 0)
+#define NMPC_COL_UNITS(U) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 0) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 1)
 #else
-        COL_CASE(1, 0) COL_CASE(2, 0) COL_CASE(3, 0) COL_CASE(4, 0) COL_CASE(5, 0)
-#if NMPC_COL_PART == 1
-    case 6: case 7: case 8: return launch_solve_col_part2(COL_ARGS);
-    case 9: case 10: return launch_solve_col_part3(COL_ARGS);
-#else
-        COL_CASE(6, 0) COL_CASE(7, 0) COL_CASE(8, 0) COL_CASE(9, 0) COL_CASE(10, 0)
+#define NMPC_COL_UNITS(U) U(1, 5, 0) U(6, 8, 0) U(9, 10, 0) U(1, 5, 1) U(6, 8, 1) U(9, 10, 1)
 #endif
+#ifdef NMPC_COL_UNIT      // instantiated in the unit's own object
+#define U(LO, HI, OBS) extern template hipError_t launch_col_unit<LO, HI, OBS>(const KParams &, const SolveVariant &, int, const SolveArgs &, hipStream_t);
+NMPC_COL_UNITS(U)
+#undef U
 #endif
-    default: return hipErrorInvalidValue;
-    }
-}
-// the same with the per-instance obstacle field P.ofield
-hipError_t launch_solve_col_obs(COL_ARGS_DECL)
+
+hipError_t launch_solve_col(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
-    switch (m) {
-#ifdef NMPC_COL_ONLY_M
-        COL_CASE(NMPC_COL_ONLY_M, 1)
-#elif NMPC_COL_PART == 1
-    case 1: case 2: case 3: case 4: case 5: return launch_solve_col_obs_part1(COL_ARGS);
-    case 6: case 7: case 8: return launch_solve_col_obs_part2(COL_ARGS);
-    case 9: case 10: return launch_solve_col_obs_part3(COL_ARGS);
-#else
-        COL_CASE(1, 1) COL_CASE(2, 1) COL_CASE(3, 1) COL_CASE(4, 1) COL_CASE(5, 1) COL_CASE(6, 1) COL_CASE(7, 1) COL_CASE(8, 1) COL_CASE(9, 1) COL_CASE(10, 1)
-#endif
-    default: return hipErrorInvalidValue;
-    }
+    if (v.kernel != KERN_COL) return hipErrorInvalidValue;
+#define U(LO, HI, OBS) if (v.m >= LO && v.m <= HI && ((v.flags & NMPC_DL_OBS) != 0) == (OBS != 0)) return launch_col_unit<LO, HI, OBS>(P, v, B, a, st);
+    NMPC_COL_UNITS(U)
+#undef U
+    return hipErrorInvalidValue;
 }
 
 bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVariant *v)
 {
-#define C_(M) (*v = ofield ? (P.thb ? select3_mt<M, 1, 1>(P, shape) : select3_mt<M, 0, 1>(P, shape)) : (P.thb ? select3_mt<M, 1, 0>(P, shape) : select3_mt<M, 0, 0>(P, shape)), true)
-    switch (m) {
-    case 1: return C_(1); case 2: return C_(2); case 3: return C_(3); case 4: return C_(4); case 5: return C_(5);
-    case 6: return C_(6); case 7: return C_(7); case 8: return C_(8); case 9: return C_(9); case 10: return C_(10);
-    default: return false;
-    }
-#undef C_
+    return for_team_size(m, false, [&](auto M) {
+        constexpr int M_ = decltype(M)::value;
+        *v = ofield ? (P.thb ? select3_mt<M_, 1, 1>(P, shape) : select3_mt<M_, 0, 1>(P, shape)) : (P.thb ? select3_mt<M_, 1, 0>(P, shape) : select3_mt<M_, 0, 0>(P, shape));
+        return true;
+    });
 }
 
 // LDS bytes one instance of the column-per-lane kernel needs in the given shape (0 if m is not supported)
 size_t col_kernel_bytes(const KParams &P, int m, int shape)
 {
-#define LB(M) case M: return P.thb ? col_lds_bytes<M, 1>(P, shape == 1 ? (M <= 6) : col_duals_in_lds<M, 1>(P), shape == 0 ? col_factor_mode<M, 1>(P) : 0) : col_lds_bytes<M, 0>(P, shape == 1 ? (M <= 6) : col_duals_in_lds<M, 0>(P), shape == 0 ? col_factor_mode<M, 0>(P) : 0);
-    switch (m) {
-        LB(1) LB(2) LB(3) LB(4) LB(5) LB(6) LB(7) LB(8) LB(9) LB(10)
-    default: return 0;
-    }
-#undef LB
+    SolveVariant v;
+    return select_solve_col(P, m, shape, false, &v) ? v.lds : 0;
 }
+#endif      // entry points
 
-#endif      // NMPC_COL_PART
-#undef COL_CASE
-#undef COL_ARGS
-#undef COL_ARGS_DECL
+#ifdef NMPC_COL_UNIT
+template hipError_t launch_col_unit<NMPC_COL_UNIT>(const KParams &, const SolveVariant &, int, const SolveArgs &, hipStream_t);
+#endif
 
 }  // namespace nmpc

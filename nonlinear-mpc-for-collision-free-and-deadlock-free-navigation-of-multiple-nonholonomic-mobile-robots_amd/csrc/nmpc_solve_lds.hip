@@ -1156,17 +1156,15 @@ template <int M_, int THB> static size_t lds_bytes(const KParams &P, int tpb)
     return d * sizeof(double);
 }
 
-template <int M_, int THB, int TPB> static hipError_t launch2_mtt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
-                                                                  int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st)
+template <int M_, int THB, int TPB> static hipError_t launch2_mtt(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
-    size_t lds = lds_bytes<M_, THB>(P, TPB);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (v.lds > 160 * 1024) return hipErrorInvalidValue;
     auto kern = solve_lds_kernel<M_, THB, TPB>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (v.lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(TPB), lds, st, P, p, w0, w_out, obj, status, iters, kkt, ws, prof);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(TPB), v.lds, st, P, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws, a.prof);
     return hipGetLastError();
 }
 
@@ -1192,81 +1190,53 @@ template <int M_, int THB> static int lds_threads(const KParams &P, int B)
 template <int M_, int THB> static SolveVariant select2_mt(const KParams &P, int B)
 {
     const int tpb = lds_threads<M_, THB>(P, B);
-    return SolveVariant{2, M_, THB, 0, tpb, lds_bytes<M_, THB>(P, tpb)};
+    return SolveVariant{KERN_LDS, M_, THB, 0, tpb, lds_bytes<M_, THB>(P, tpb)};
 }
 
-template <int M_, int THB> static hipError_t launch2_mt(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj,
-                                                        int32_t *status, int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st)
+// the instantiation whose template arguments are v's
+template <int M_, int THB> static hipError_t launch2_mt(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
-    const int tpb = select2_mt<M_, THB>(P, B).threads;
     if constexpr (M_ == 5 || M_ == 6) {
-        if (tpb == 256) return launch2_mtt<M_, THB, 256>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-        if (tpb == 128) return launch2_mtt<M_, THB, 128>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
+        if (v.threads == 256) return launch2_mtt<M_, THB, 256>(P, v, B, a, st);
+        if (v.threads == 128) return launch2_mtt<M_, THB, 128>(P, v, B, a, st);
     }
     constexpr int TPB = lds_tp_threads<M_>();
-    if (tpb != TPB) return hipErrorInvalidValue;
-    return launch2_mtt<M_, THB, TPB>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-}
-template <int M_> static hipError_t launch2_m(const KParams &P, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                                              int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st)
-{
-    return P.thb ? launch2_mt<M_, 1>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st)
-                 : launch2_mt<M_, 0>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
+    if (v.threads != TPB) return hipErrorInvalidValue;
+    return launch2_mtt<M_, THB, TPB>(P, v, B, a, st);
 }
 
-hipError_t launch_solve_lds(const KParams &P, int m, int B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
-                            int32_t *iters, double *kkt, double *ws, long long *prof, hipStream_t st)
+hipError_t launch_solve_lds(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
-    switch (m) {
-    case 1: return launch2_m<1>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 2: return launch2_m<2>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 3: return launch2_m<3>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 4: return launch2_m<4>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 5: return launch2_m<5>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 6: return launch2_m<6>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 7: return launch2_m<7>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 8: return launch2_m<8>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 9: return launch2_m<9>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    case 10: return launch2_m<10>(P, B, p, w0, w_out, obj, status, iters, kkt, ws, prof, st);
-    default: return hipErrorInvalidValue;
-    }
+    if (v.kernel != KERN_LDS) return hipErrorInvalidValue;
+    return for_team_size(v.m, hipErrorInvalidValue, [&](auto M) {
+        constexpr int M_ = decltype(M)::value;
+        return v.thb ? launch2_mt<M_, 1>(P, v, B, a, st) : launch2_mt<M_, 0>(P, v, B, a, st);
+    });
 }
 
 bool select_solve_lds(const KParams &P, int m, int B, SolveVariant *v)
 {
-#define C_(M) (*v = P.thb ? select2_mt<M, 1>(P, B) : select2_mt<M, 0>(P, B), true)
-    switch (m) {
-    case 1: return C_(1); case 2: return C_(2); case 3: return C_(3); case 4: return C_(4); case 5: return C_(5);
-    case 6: return C_(6); case 7: return C_(7); case 8: return C_(8); case 9: return C_(9); case 10: return C_(10);
-    default: return false;
-    }
-#undef C_
+    return for_team_size(m, false, [&](auto M) {
+        constexpr int M_ = decltype(M)::value;
+        return *v = P.thb ? select2_mt<M_, 1>(P, B) : select2_mt<M_, 0>(P, B), true;
+    });
 }
 
 // LDS bytes one instance of the LDS-resident kernel needs in its throughput shape (0 if m is not supported); the C ABI falls
 // back to the HBM-resident kernel when this exceeds the 160 KB of a CU
 size_t lds_kernel_bytes(const KParams &P, int m)
 {
-#define LB(M) case M: return P.thb ? lds_bytes<M, 1>(P, lds_tp_threads<M>()) : lds_bytes<M, 0>(P, lds_tp_threads<M>());
-    switch (m) {
-        LB(1) LB(2) LB(3) LB(4) LB(5) LB(6) LB(7) LB(8) LB(9) LB(10)
-    default: return 0;
-    }
-#undef LB
+    return for_team_size(m, (size_t)0, [&](auto M) {
+        constexpr int M_ = decltype(M)::value;
+        return P.thb ? lds_bytes<M_, 1>(P, lds_tp_threads<M_>()) : lds_bytes<M_, 0>(P, lds_tp_threads<M_>());
+    });
 }
 
 // workspace doubles per instance for this kernel (packs + transposed gains)
 void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride)
 {
-    const int thb = P.thb;
-    int64_t pack = 0, kts = 0;
-#define SZ(M)                                                                                                                     \
-    case M:                                                                                                                       \
-        pack = thb ? G2<M, 1>::PACK : G2<M, 0>::PACK;                                                                             \
-        kts = thb ? G2<M, 1>::KTS : G2<M, 0>::KTS;                                                                                \
-        break;
-    switch (m) { SZ(1) SZ(2) SZ(3) SZ(4) SZ(5) SZ(6) SZ(7) SZ(8) SZ(9) SZ(10) default: break; }
-#undef SZ
+    const int64_t pack = for_team_size(m, (int64_t)0, [&](auto M) { return (int64_t)(P.thb ? G2<decltype(M)::value, 1>::PACK : G2<decltype(M)::value, 0>::PACK); });
+    const int64_t kts = for_team_size(m, (int64_t)0, [&](auto M) { return (int64_t)(P.thb ? G2<decltype(M)::value, 1>::KTS : G2<decltype(M)::value, 0>::KTS); });
     int64_t o = 0;
     *pack_off = o; o += (int64_t)(P.N + 1) * pack; o = (o + 15) / 16 * 16;
     *kt_off = o; o += (int64_t)P.N * kts; o = (o + 15) / 16 * 16;

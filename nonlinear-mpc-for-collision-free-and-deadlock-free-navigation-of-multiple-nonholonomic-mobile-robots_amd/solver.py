@@ -158,6 +158,15 @@ class NmpcSolver:
         return self.lib.nmpc_solve_batch_duals(self._h, 0, None, None, 0, None, None, None, None, None, None, None, None, None) == 0
 
     # ---- batched device API -----------------------------------------------------------------
+    def _order(self, order, B):
+        """a dispatch-order hint as the int32 device tensor the C ABI reads (None stays None)"""
+        if order is None:
+            return None
+        od = self.torch.as_tensor(order, device=self.device).to(self.torch.int32).contiguous()
+        if od.shape != (B,):
+            raise ValueError(f"order must have shape ({B},)")
+        return od
+
     def solve_batch(self, p, w0, want_fg: bool = False, order=None, obstacles=None, want_duals: bool = False):
         """p [B, 2 n_x], w0 [B, n_var] (torch cuda / numpy) -> dict of torch cuda tensors.
 
@@ -180,32 +189,20 @@ class NmpcSolver:
         iters = torch.empty(B, dtype=torch.int32, device=self.device)
         lam = {}
         with torch.cuda.device(self.device):
+            od = self._order(order, B)
             if want_duals:
-                od = None
-                if order is not None:
-                    od = torch.as_tensor(order, device=self.device).to(torch.int32).contiguous()
-                    if od.shape != (B,):
-                        raise ValueError(f"order must have shape ({B},)")
                 lam, cd = self._duals(B)
                 _lib.check(self.lib.nmpc_solve_batch_duals(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
                                                            w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
                                                            od.data_ptr() if od is not None else None, C.byref(cd), self._stream()), "nmpc_solve_batch_duals")
             elif ob is not None:
-                od = None
-                if order is not None:
-                    od = torch.as_tensor(order, device=self.device).to(torch.int32).contiguous()
-                    if od.shape != (B,):
-                        raise ValueError(f"order must have shape ({B},)")
                 _lib.check(self.lib.nmpc_solve_batch_obs(self._h, B, p.data_ptr(), ob[0].data_ptr(), ob[1], w0.data_ptr(), w.data_ptr(), obj.data_ptr(),
                                                          status.data_ptr(), iters.data_ptr(), kkt.data_ptr(), od.data_ptr() if od is not None else None,
                                                          self._stream()), "nmpc_solve_batch_obs")
-            elif order is None:
+            elif od is None:
                 _lib.check(self.lib.nmpc_solve_batch(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(),
                                                      status.data_ptr(), iters.data_ptr(), kkt.data_ptr(), self._stream()), "nmpc_solve_batch")
             else:
-                od = torch.as_tensor(order, device=self.device).to(torch.int32).contiguous()
-                if od.shape != (B,):
-                    raise ValueError(f"order must have shape ({B},)")
                 _lib.check(self.lib.nmpc_solve_batch_ordered(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(),
                                                              iters.data_ptr(), kkt.data_ptr(), od.data_ptr(), self._stream()), "nmpc_solve_batch_ordered")
         out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt, **lam)

@@ -106,14 +106,6 @@ def closed_loop_oracle(ocfg, x0, goals, max_steps, stop_tol=5e-2, max_iter=2000,
     return dict(steps=steps, arrived=arrived, arrival_step=arrival, final_error=err, states=np.stack(states), failed_solves=failed)
 
 
-def to_oracle_cfg(pcfg):
-    """product ProblemConfig -> oracle NLPConfig (for the script presets, whose literals tests/test_abi_host.py checks
-    against its own table)."""
-    return R.NLPConfig(m=pcfg.m, N=pcfg.N, T=pcfg.T, dmin=pcfg.dmin, q=tuple(pcfg.q), r=tuple(pcfg.r), v_max=pcfg.v_max, w_max=pcfg.w_max,
-                       xy_max=pcfg.xy_max, th_max=pcfg.th_max, obstacles=list(pcfg.obstacles), rob_dim=pcfg.rob_dim, margin=pcfg.margin,
-                       pad_value=pcfg.pad_value, pad_rows=pcfg.pad_rows, pair_rows=pcfg.pair_rows)
-
-
 def lidar_closed_loop_oracle(cfg, pose0, goals, world, max_steps, arrive_tol=0.2, scan_max=3.5, lbx=None, ubx=None, max_iter=2000):
     """The main loop of obs_avoid_static_first_scenario_v4.py (V4:209-300) driven by the CPU oracle on a synthetic world of circular
     obstacles — checker for nmpc_amd.simulate_lidar_closed_loop: scan (callback_lidar V4:29-36 -> lidar_ref.scan_of_world), p (V4:230-236),

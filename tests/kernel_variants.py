@@ -19,7 +19,7 @@ horizon with the duals out of LDS (DUALS_OUT), with the stage factors out of LDS
 library runs on the HBM-resident kernel (KERNEL1); they depend on (m, heading flag, number of obstacles).  A pin (nmpc_options_t.kernel) is
 used only where the library's own choice cannot reach the row:
   * the latency shape up to three robots (pin 4): the library's own choice for them is the throughput shape at every batch size;
-  * every element-per-lane row (pin 2): the library's own choice never launches that kernel.  kernel_for_batch() takes it where the column
+  * every element-per-lane row (pin 2): the library's own choice never launches that kernel.  solve_plan() takes it where the column
     kernel's latency shape does not fit the LDS and the element-per-lane kernel does, but for every team size, heading flag and obstacle
     count the element-per-lane kernel outgrows the 160 KB first (five robots, no obstacles: N = 113 against N = 120; six: 89 against 97;
     from seven robots on the latency shape is the throughput shape's size and the handle leaves the column kernel with it).
@@ -148,6 +148,23 @@ TABLE = [r._replace(seed=SEEDS.get(r.row, r.seed)) for r in TABLE]
 
 def row_id(r):
     return "k%d-m%d-thb%d-dl%d-t%d" % r.row
+
+
+def c_config(cfg, max_iter):
+    """the nmpc_config_t of an oracle config"""
+    return Hh.to_product_cfg(cfg, max_iter=max_iter).to_c()
+
+
+def variant_of_config(cc, pin, cus, B, ordered, obs_field):
+    """nmpc_debug_variant_of_config on an nmpc_config_t: (return code, (kernel, m, thb, flags, threads), LDS bytes, kernel code 1..4) of the
+    launch a handle with that pin makes on a device with `cus` compute units; needs no handle and no device"""
+    import ctypes as C
+    import nmpc_amd
+    lib = nmpc_amd._lib
+    v, k = lib.CDebugVariant(), C.c_int32(0)
+    rc = lib.load().nmpc_debug_variant_of_config(C.byref(cc), C.byref(lib.COptions(kernel=pin, trace_instance=-1)), cus, B, int(ordered), int(bool(obs_field)),
+                                                C.byref(v), C.byref(k))
+    return rc, (v.kernel, v.m, v.thb, v.flags, v.threads), int(v.lds_bytes), k.value
 
 
 def near_batch(cfg, B, seed, radius):

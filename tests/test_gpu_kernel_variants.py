@@ -62,6 +62,11 @@ def _abi_solve(L, h, cfg, P, W0, F, order):
     return out
 
 
+def _compute_units():
+    import torch
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
 def _order(B, seed):
     return np.random.default_rng(seed).permutation(B).astype(np.int32)
 
@@ -79,6 +84,7 @@ def test_variant_solves_like_the_oracle(built, capsys, r):
     try:
         rc, got, lds = _variant(L, h, B, r.ordered, r.obs_field)
         assert rc == 0 and got == r.row, ("the recipe launches another instantiation", r.row, rc, got)
+        assert (rc, got, lds) == KV.variant_of_config(KV.c_config(cfg, r.max_iter), r.pin, _compute_units(), B, r.ordered, r.obs_field)[:3]
         out = _abi_solve(L, h, cfg, P, W0, F, _order(B, 3) if r.ordered else None)
     finally:
         L.nmpc_destroy(h)
