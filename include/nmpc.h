@@ -268,6 +268,25 @@ int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const doubl
                        const double *lam_x, double *res /* [B][6] */, double *grad_lag /* [B][n_var] or NULL */, void *stream);
 
 /*
+ * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and
+ * nmpc_kkt_batch with the pose reference of every instance given apart from p, one row for the horizon or one per stage (the tutorial
+ * lineage of the scripts carries it as P = [x0; x_ref,1 .. x_ref,N]; AS/mpc_control_trajectory_tracking.py tracks a path on its SLSQP route):
+ *   ref [B][S][n_x] fp64 device, S = ref_stages, 1 or N.
+ *   Stage k's cost term (k = 0..N-1, at X_k) is (X_k - xs_k)' Q (X_k - xs_k) with xs_k row k when S == N and row 0 when S == 1.  The xs half of
+ *   p is not read by these calls; the x0 half is read as always.
+ * (obs, obs_stages): obs == NULL and obs_stages == 0 is the handle's own obstacle field, otherwise the per-instance field by the rules of the
+ * *_obs calls.  The row layout, n_g and the bounds are those of the plain calls; g does not depend on the reference, and given ref equal to the
+ * xs half of p (either S) the outputs are those of the plain calls.  In nmpc_kkt_batch_ref, grad f of stage k is 2 Q (X_k - xs_k): a point whose
+ * multipliers certify it here is a KKT point of the tracking problem, whoever computed it.  The solve calls take no per-stage reference yet.
+ * Returns NMPC_E_ARG when ref == NULL with B > 0, when ref_stages is neither 1 nor N, or for the argument errors of the *_obs calls.  Both
+ * work on every handle, like nmpc_eval_batch.
+ */
+int32_t nmpc_eval_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *ref, int32_t ref_stages, const double *obs,
+                            int32_t obs_stages, double *f, double *g, void *stream);
+int32_t nmpc_kkt_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *ref, int32_t ref_stages, const double *obs, int32_t obs_stages,
+                           const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag /* [B][n_var] or NULL */, void *stream);
+
+/*
  * Odometry front-end of the scripts' callbacks (AS/centralized_two_robots_implementation.py:18-37): for n robots,
  *   odom [n][4] = (x_r, y_r, q_z, q_w) wheel-odometry pose in the robot's own start frame (q_w is carried but, as in the
  *                  reference, not used: yaw = 2 asin(q_z)),

@@ -24,7 +24,8 @@ DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", 
 QUERY_KERNEL_FOR_BATCH, QUERY_WORKSPACE_BYTES, QUERY_LDS_BYTES, QUERY_MAX_BATCH, QUERY_KERNEL_FOR_ORDERED_BATCH = 1, 2, 3, 4, 5      # NMPC_QUERY_* of include/nmpc.h
 EXPORTS = ["nmpc_n_var", "nmpc_n_g", "nmpc_n_p", "nmpc_config_default", "nmpc_create", "nmpc_create_opts", "nmpc_query", "nmpc_destroy",
            "nmpc_workspace_bytes", "nmpc_solve_batch", "nmpc_solve_batch_ordered", "nmpc_step_batch", "nmpc_eval_batch", "nmpc_shift_batch", "nmpc_odometry_batch", "nmpc_version",
-           "nmpc_solve_batch_obs", "nmpc_step_batch_obs", "nmpc_eval_batch_obs", "nmpc_solve_batch_duals", "nmpc_step_batch_duals", "nmpc_kkt_batch"]
+           "nmpc_solve_batch_obs", "nmpc_step_batch_obs", "nmpc_eval_batch_obs", "nmpc_solve_batch_duals", "nmpc_step_batch_duals", "nmpc_kkt_batch",
+           "nmpc_eval_batch_ref", "nmpc_kkt_batch_ref"]
 
 
 class CConfig(C.Structure):
@@ -108,6 +109,8 @@ def load():
     L.nmpc_solve_batch_duals.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, dp, vp]; L.nmpc_solve_batch_duals.restype = i32
     L.nmpc_step_batch_duals.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, dp, vp]; L.nmpc_step_batch_duals.restype = i32
     L.nmpc_kkt_batch.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]; L.nmpc_kkt_batch.restype = i32
+    L.nmpc_eval_batch_ref.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp]; L.nmpc_eval_batch_ref.restype = i32
+    L.nmpc_kkt_batch_ref.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]; L.nmpc_kkt_batch_ref.restype = i32
     L.nmpc_shift_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]; L.nmpc_shift_batch.restype = i32
     L.nmpc_odometry_batch.argtypes = [C.c_int64, vp, vp, vp, i32, vp]; L.nmpc_odometry_batch.restype = i32
     L.nmpc_version.argtypes = []; L.nmpc_version.restype = C.c_char_p

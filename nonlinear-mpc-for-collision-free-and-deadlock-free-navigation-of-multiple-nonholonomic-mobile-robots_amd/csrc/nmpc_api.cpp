@@ -284,6 +284,21 @@ static void set_field(nmpc::KParams *P, const nmpc_config_t &cfg, const double *
     P->ofield.sstride = obs_stages == 1 ? 0 : cfg.n_obs * 3;
 }
 
+// the pose reference of an eval / kkt call as the kernels read it: ref [B][ref_stages][n_x] of the *_ref entry points (checked by ref_check), or,
+// ref == nullptr, the xs half of p
+static nmpc::PoseRef pose_ref(const nmpc_config_t &cfg, const double *p, const double *ref, int32_t ref_stages)
+{
+    const int32_t nx = 3 * cfg.m;
+    if (!ref) return nmpc::PoseRef{p + nx, 2 * nx, 0};
+    return nmpc::PoseRef{ref, ref_stages * nx, ref_stages == cfg.N ? nx : 0};
+}
+
+// the checks of the *_ref entry points on their reference argument, after call_check
+static int32_t ref_check(const nmpc_handle_t *h, int32_t B, const double *ref, int32_t ref_stages)
+{
+    return ((ref_stages != 1 && ref_stages != h->cfg.N) || (B > 0 && !ref)) ? NMPC_E_ARG : NMPC_OK;
+}
+
 static bool wants_duals(const nmpc_duals_t *d) { return d && (d->lam_g || d->lam_x || d->lam_p); }
 
 // obs != NULL: the obstacle field of the instances, [B][obs_stages][n_obs][3] (checked by call_check), read by the column kernel's
@@ -369,30 +384,32 @@ int32_t nmpc_step_batch_obs(nmpc_handle_t *h, int32_t B, double *p, double *w, d
     return rc != NMPC_OK ? rc : step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages);
 }
 
-int32_t nmpc_eval_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *w, double *f, double *g, void *stream)
+// the evaluation of f and g behind the three eval entry points, after their checks: obs (or nullptr: the handle's own field) and ref (or
+// nullptr: the xs half of p) by the same rule
+static int32_t eval_impl(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *ref, int32_t ref_stages, const double *obs,
+                         int32_t obs_stages, double *f, double *g, void *stream)
 {
-    if (!h || B < 0) return NMPC_E_ARG;
     if (B == 0) return NMPC_OK;
     if (!p || !w) return NMPC_E_ARG;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
-    hipError_t e = nmpc::launch_eval(h->P, h->cfg.m, B, p, w, f, g, (hipStream_t)stream);
+    nmpc::KParams P = h->P;
+    if (obs) set_field(&P, h->cfg, obs, obs_stages);
+    hipError_t e = nmpc::launch_eval(P, pose_ref(h->cfg, p, ref, ref_stages), h->cfg.m, B, p, w, f, g, (hipStream_t)stream, obs != nullptr);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+int32_t nmpc_eval_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *w, double *f, double *g, void *stream)
+{
+    if (!h || B < 0) return NMPC_E_ARG;
+    return eval_impl(h, B, p, w, nullptr, 0, nullptr, 0, f, g, stream);
 }
 
 int32_t nmpc_eval_batch_obs(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *obs, int32_t obs_stages, double *f, double *g,
                             void *stream)
 {
     const int32_t rc = call_check(h, B, obs, obs_stages, 0);
-    if (rc != NMPC_OK) return rc;
-    if (B == 0) return NMPC_OK;
-    if (!p || !w) return NMPC_E_ARG;
-    DeviceScope dev(h->device);
-    if (!dev.ok) return NMPC_E_HIP;
-    nmpc::KParams P = h->P;
-    set_field(&P, h->cfg, obs, obs_stages);
-    hipError_t e = nmpc::launch_eval(P, h->cfg.m, B, p, w, f, g, (hipStream_t)stream, true);
-    return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+    return rc != NMPC_OK ? rc : eval_impl(h, B, p, w, nullptr, 0, obs, obs_stages, f, g, stream);
 }
 
 int32_t nmpc_solve_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w0, double *w_out,
@@ -409,19 +426,41 @@ int32_t nmpc_step_batch_duals(nmpc_handle_t *h, int32_t B, double *p, double *w,
     return rc != NMPC_OK ? rc : step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages, duals);
 }
 
-int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
-                       const double *lam_x, double *res, double *grad_lag, void *stream)
+static int32_t kkt_impl(nmpc_handle_t *h, int32_t B, const double *p, const double *ref, int32_t ref_stages, const double *obs, int32_t obs_stages,
+                        const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag, void *stream)
 {
-    const int32_t rc = call_check(h, B, obs, obs_stages, CK_OPT_FIELD);
-    if (rc != NMPC_OK) return rc;
     if (B == 0) return NMPC_OK;
     if (!p || !w || !lam_g || !lam_x || !res) return NMPC_E_ARG;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
     nmpc::KParams P = h->P;
     if (obs) set_field(&P, h->cfg, obs, obs_stages);
-    hipError_t e = nmpc::launch_kkt(P, h->cfg.m, B, p, w, lam_g, lam_x, res, grad_lag, (hipStream_t)stream, obs != nullptr);
+    hipError_t e = nmpc::launch_kkt(P, pose_ref(h->cfg, p, ref, ref_stages), h->cfg.m, B, p, w, lam_g, lam_x, res, grad_lag, (hipStream_t)stream, obs != nullptr);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                       const double *lam_x, double *res, double *grad_lag, void *stream)
+{
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_OPT_FIELD);
+    return rc != NMPC_OK ? rc : kkt_impl(h, B, p, nullptr, 0, obs, obs_stages, w, lam_g, lam_x, res, grad_lag, stream);
+}
+
+/* ---- the *_ref entry points: a pose reference per instance, one row or one per stage, in place of the xs half of p */
+int32_t nmpc_eval_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *ref, int32_t ref_stages, const double *obs,
+                            int32_t obs_stages, double *f, double *g, void *stream)
+{
+    int32_t rc = call_check(h, B, obs, obs_stages, CK_OPT_FIELD);
+    if (rc == NMPC_OK) rc = ref_check(h, B, ref, ref_stages);
+    return rc != NMPC_OK ? rc : eval_impl(h, B, p, w, ref, ref_stages, obs, obs_stages, f, g, stream);
+}
+
+int32_t nmpc_kkt_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *ref, int32_t ref_stages, const double *obs, int32_t obs_stages,
+                           const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag, void *stream)
+{
+    int32_t rc = call_check(h, B, obs, obs_stages, CK_OPT_FIELD);
+    if (rc == NMPC_OK) rc = ref_check(h, B, ref, ref_stages);
+    return rc != NMPC_OK ? rc : kkt_impl(h, B, p, ref, ref_stages, obs, obs_stages, w, lam_g, lam_x, res, grad_lag, stream);
 }
 
 int32_t nmpc_shift_batch(nmpc_handle_t *h, int32_t B, const double *p_in, const double *w_in, double *w_next, double *x0_next, void *stream)

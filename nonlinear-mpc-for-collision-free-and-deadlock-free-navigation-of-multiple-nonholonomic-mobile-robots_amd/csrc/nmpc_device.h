@@ -48,6 +48,15 @@ struct KParams {
     int32_t oX, oU, oLAM, oS, oZ, oDX, oDU, oLAMN, oDS, oDZ, oSN, oCS, oC, oH, oGX, oHUU, oGU, oHVT, oHTT, oKG, oKFF, oCKP, oEL;      // oCKP: the HBM-resident kernel's saved cost-to-go, [(N-1)/NMPC_CKPT_EVERY + 1][nx * nx + nx]; oEL: its elastic variables, one per inequality slot
 };
 
+// The pose reference of the cost as eval_kernel and kkt_residual_kernel read it, sum_k (X_k - xs_k)' Q (X_k - xs_k): instance b's rows start at
+// ptr + b * istride and stage k reads row k * sstride.  The plain calls point it at the xs half of p (ptr = p + n_x, istride = 2 n_x, sstride = 0),
+// the *_ref calls at ref [B][S][n_x] (istride = S n_x; sstride = n_x when S = N, else 0).  A kernel argument of its own: KParams, which the solve
+// kernels share, keeps its layout.
+struct PoseRef {
+    const double *ptr;
+    int32_t istride, sstride;
+};
+
 // The solve kernels by the code nmpc_options_t.kernel pins and NMPC_QUERY_KERNEL_FOR_BATCH answers (include/nmpc.h), and the shapes of the
 // column kernel: one, two or four wavefronts per instance.  KERN_COL_LAT is the column kernel in one of its two latency shapes.
 enum { KERN_HBM = 1, KERN_LDS = 2, KERN_COL = 3, KERN_COL_LAT = 4 };
@@ -79,9 +88,9 @@ hipError_t launch_solve_col(const KParams &P, const SolveVariant &v, int B, cons
 size_t lds_kernel_bytes(const KParams &P, int m);                 // the element-per-lane kernel's throughput shape
 size_t col_kernel_bytes(const KParams &P, int m, int shape);      // = select_solve_col(..).lds
 void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride);
-hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
+hipError_t launch_eval(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
 // KKT residuals of (w, lam_g, lam_x): res [B][6] = (stat, eq, ineq, bnd, compl, sign), grad_lag [B][nvar] or nullptr (include/nmpc.h, nmpc_kkt_batch)
-hipError_t launch_kkt(const KParams &P, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
+hipError_t launch_kkt(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
                       hipStream_t st, bool ofield);
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);

@@ -882,7 +882,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
 // nmpc_solve_common.h) — a bit of the template argument, as the column kernel's DL, so that the plain instantiations keep their names and code.
 constexpr int NMPC_EVAL_OBS = 16;
 template <int MS>
-__global__ __launch_bounds__(256) void eval_kernel(const KParams P, int B, const double *__restrict__ p_in, const double *__restrict__ w,
+__global__ __launch_bounds__(256) void eval_kernel(const KParams P, const PoseRef XR, int B, const double *__restrict__ p_in, const double *__restrict__ w,
                                                     double *__restrict__ f_out, double *__restrict__ g_out)
 {
     constexpr int M_ = MS % NMPC_EVAL_OBS, OS = MS / NMPC_EVAL_OBS;
@@ -902,13 +902,14 @@ __global__ __launch_bounds__(256) void eval_kernel(const KParams P, int B, const
         return;
     }
     const double *x = X + (size_t)k * NX, *xn = x + NX, *u = U + (size_t)k * NU;
+    const double *xs = XR.ptr + (size_t)b * XR.istride + (size_t)k * XR.sstride;      // the pose reference of stage k (PoseRef: the xs half of p, or a row of ref)
     double fs = 0.0;
     double *gk = g ? g + P.rows0 + (size_t)k * P.rowsk : nullptr;
 #pragma unroll
     for (int i = 0; i < M_; i++) {
         double s, c;
         sincos(x[3 * i + 2], &s, &c);
-        double e0 = x[3 * i] - pp[NX + 3 * i], e1 = x[3 * i + 1] - pp[NX + 3 * i + 1], e2 = x[3 * i + 2] - pp[NX + 3 * i + 2];
+        double e0 = x[3 * i] - xs[3 * i], e1 = x[3 * i + 1] - xs[3 * i + 1], e2 = x[3 * i + 2] - xs[3 * i + 2];
         fs += P.q[0] * e0 * e0 + P.q[1] * e1 * e1 + P.q[2] * e2 * e2 + P.r[0] * u[2 * i] * u[2 * i] + P.r[1] * u[2 * i + 1] * u[2 * i + 1];
         if (gk) {
             gk[3 * i] = xn[3 * i] - (x[3 * i] + P.T * u[2 * i] * c);
@@ -941,7 +942,7 @@ __global__ __launch_bounds__(256) void eval_kernel(const KParams P, int B, const
 // reduced with an integer atomic max on their bit patterns (same order; a NaN ranks above every number, so it reaches the result).
 __device__ __forceinline__ void kkt_max(double &a, double v) { a = (v > a || v != v) ? v : a; }      // a starts at 0: the positive part; fmax would drop a NaN
 template <int MS>
-__global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, int B, const double *__restrict__ p_in, const double *__restrict__ w,
+__global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, const PoseRef XR, int B, const double *__restrict__ p_in, const double *__restrict__ w,
                                                             const double *__restrict__ lam_g, const double *__restrict__ lam_x,
                                                             double *__restrict__ res_out, double *__restrict__ grad_out)
 {
@@ -957,6 +958,7 @@ __global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, int 
     double *gX = grad_out ? grad_out + (size_t)b * P.nvar + (size_t)k * NX : nullptr;
     double *gU = grad_out ? grad_out + (size_t)b * P.nvar + (size_t)(N + 1) * NX + (size_t)k * NU : nullptr;
     const double *x = X + (size_t)k * NX;
+    const double *xs = XR.ptr + (size_t)b * XR.istride + (size_t)k * XR.sstride;      // the pose reference of stage k, read for k < N only (as eval_kernel)
     const double *lk = lg + P.rows0 + (size_t)k * P.rowsk;            // multipliers of stage k's block: defect k, pair rows, obstacle rows (k < N)
     const double *lprev = lk - P.rowsk;                                // defect k-1 (k >= 1)
     const int npairs = P.pairs ? NP : 0;
@@ -987,9 +989,9 @@ __global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, int 
             const double l0 = lk[3 * i], l1 = lk[3 * i + 1], l2 = lk[3 * i + 2], v = u[0], om = u[1];
             double s, c;
             sincos(th, &s, &c);
-            g0 += 2.0 * P.q[0] * (xi - pp[NX + 3 * i]) - l0;
-            g1 += 2.0 * P.q[1] * (yi - pp[NX + 3 * i + 1]) - l1;
-            g2 += 2.0 * P.q[2] * (th - pp[NX + 3 * i + 2]) - l2 + P.T * v * (s * l0 - c * l1);
+            g0 += 2.0 * P.q[0] * (xi - xs[3 * i]) - l0;
+            g1 += 2.0 * P.q[1] * (yi - xs[3 * i + 1]) - l1;
+            g2 += 2.0 * P.q[2] * (th - xs[3 * i + 2]) - l2 + P.T * v * (s * l0 - c * l1);
             kkt_max(eq, fabs(xn[3 * i] - (xi + P.T * v * c))); kkt_max(eq, fabs(xn[3 * i + 1] - (yi + P.T * v * s))); kkt_max(eq, fabs(xn[3 * i + 2] - (th + P.T * om)));
             for (int j = 0; j < (P.pairs ? M_ : 0); j++) {
                 if (j == i) continue;
@@ -1069,26 +1071,26 @@ template <int M_> static hipError_t launch_solve_m(const KParams &P, const Solve
     hipLaunchKernelGGL((solve_kernel<M_, TPB>), dim3(B), dim3(TPB), 0, st, P, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws);
     return hipGetLastError();
 }
-template <int M_> static hipError_t launch_eval_m(const KParams &P, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
+template <int M_> static hipError_t launch_eval_m(const KParams &P, const PoseRef &xr, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
 {
     if (f) { hipError_t e = hipMemsetAsync(f, 0, sizeof(double) * (size_t)B, st); if (e != hipSuccess) return e; }
     long total = (long)B * (P.N + 1);
     if (ofield)
-        hipLaunchKernelGGL((eval_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
+        hipLaunchKernelGGL((eval_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, xr, B, p, w, f, g);
     else
-        hipLaunchKernelGGL((eval_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, f, g);
+        hipLaunchKernelGGL((eval_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, xr, B, p, w, f, g);
     return hipGetLastError();
 }
-template <int M_> static hipError_t launch_kkt_m(const KParams &P, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res,
+template <int M_> static hipError_t launch_kkt_m(const KParams &P, const PoseRef &xr, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res,
                                                  double *grad_lag, hipStream_t st, bool ofield)
 {
     hipError_t e = hipMemsetAsync(res, 0, sizeof(double) * 6 * (size_t)B, st);      // the maxima start at +0
     if (e != hipSuccess) return e;
     long total = (long)B * (P.N + 1);
     if (ofield)
-        hipLaunchKernelGGL((kkt_residual_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, lam_g, lam_x, res, grad_lag);
+        hipLaunchKernelGGL((kkt_residual_kernel<M_ + NMPC_EVAL_OBS>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, xr, B, p, w, lam_g, lam_x, res, grad_lag);
     else
-        hipLaunchKernelGGL((kkt_residual_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w, lam_g, lam_x, res, grad_lag);
+        hipLaunchKernelGGL((kkt_residual_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, xr, B, p, w, lam_g, lam_x, res, grad_lag);
     return hipGetLastError();
 }
 template <int M_> static hipError_t launch_shift_m(const KParams &P, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st)
@@ -1189,14 +1191,14 @@ bool select_solve(const KParams &, int m, int, SolveVariant *v)
 {
     return for_team_size(m, false, [&](auto M) { return *v = SolveVariant{KERN_HBM, decltype(M)::value, 0, 0, solve_threads<decltype(M)::value>(), 0}, true; });
 }
-hipError_t launch_eval(const KParams &P, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
+hipError_t launch_eval(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield)
 {
-    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_eval_m<decltype(M)::value>(P, B, p, w, f, g, st, ofield); });
+    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_eval_m<decltype(M)::value>(P, xr, B, p, w, f, g, st, ofield); });
 }
-hipError_t launch_kkt(const KParams &P, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
+hipError_t launch_kkt(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
                       hipStream_t st, bool ofield)
 {
-    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_kkt_m<decltype(M)::value>(P, B, p, w, lam_g, lam_x, res, grad_lag, st, ofield); });
+    return for_team_size(m, hipErrorInvalidValue, [&](auto M) { return launch_kkt_m<decltype(M)::value>(P, xr, B, p, w, lam_g, lam_x, res, grad_lag, st, ofield); });
 }
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st)
 {

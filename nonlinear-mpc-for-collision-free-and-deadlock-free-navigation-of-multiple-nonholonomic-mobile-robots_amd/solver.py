@@ -145,6 +145,17 @@ class NmpcSolver:
             raise ValueError(f"obstacles must have shape ({B}, {K}, 3) or ({B}, {N}, {K}, 3), got {tuple(o.shape)}")
         return o.contiguous(), int(o.shape[1])
 
+    def _reference(self, reference, B):
+        """The pose reference of a call: [B, n_x] (one row for the horizon, S = 1) or [B, N, n_x] (row k: the reference of X_k, S = N)
+        -> (contiguous float64 device tensor [B, S, n_x], S)."""
+        nx, N = self.cfg.nx, self.cfg.N
+        r = self.torch.as_tensor(reference, dtype=self.torch.float64, device=self.device)
+        if r.dim() == 2 and tuple(r.shape) == (B, nx):
+            r = r.reshape(B, 1, nx)
+        elif not (r.dim() == 3 and tuple(r.shape) in ((B, N, nx), (B, 1, nx))):      # [B, 1, n_x]: the C ABI's S = 1
+            raise ValueError(f"reference must have shape ({B}, {nx}) or ({B}, {N}, {nx}), got {tuple(r.shape)}")
+        return r.contiguous(), int(r.shape[1])
+
     def _duals(self, B):
         """the multiplier outputs of a *_duals call: dict(lam_g [B, n_g], lam_x [B, n_var], lam_p [B, n_p]) of device tensors and their nmpc_duals_t"""
         torch = self.torch
@@ -247,8 +258,9 @@ class NmpcSolver:
                                                 kkt.data_ptr(), order.data_ptr() if order is not None else None, self._stream()), "nmpc_step_batch")
         return dict(x=x, f=obj, status=status, iters=iters, kkt=kkt, order=order)
 
-    def eval_batch(self, p, w, obstacles=None):
-        """f [B] and g [B, n_g] at w (nmpc_eval_batch); obstacles: optional per-instance obstacle field (nmpc_eval_batch_obs), as in solve_batch."""
+    def eval_batch(self, p, w, obstacles=None, reference=None):
+        """f [B] and g [B, n_g] at w (nmpc_eval_batch); obstacles: optional per-instance obstacle field (nmpc_eval_batch_obs), reference: optional
+        pose reference of the cost (nmpc_eval_batch_ref), [B, n_x] or [B, N, n_x] (row k: where X_k should be); the xs half of p is then not used."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w = self._dev(w, (B, self.n_var))
@@ -256,6 +268,11 @@ class NmpcSolver:
         f = torch.empty(B, dtype=torch.float64, device=self.device)
         g = torch.empty((B, self.n_g), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
+            if reference is not None:
+                rf = self._reference(reference, B)
+                _lib.check(self.lib.nmpc_eval_batch_ref(self._h, B, p.data_ptr(), w.data_ptr(), rf[0].data_ptr(), rf[1], ob[0].data_ptr() if ob is not None else None,
+                                                        ob[1] if ob is not None else 0, f.data_ptr(), g.data_ptr(), self._stream()), "nmpc_eval_batch_ref")
+                return f, g
             if ob is not None:
                 _lib.check(self.lib.nmpc_eval_batch_obs(self._h, B, p.data_ptr(), w.data_ptr(), ob[0].data_ptr(), ob[1], f.data_ptr(), g.data_ptr(),
                                                         self._stream()), "nmpc_eval_batch_obs")
@@ -263,10 +280,10 @@ class NmpcSolver:
             _lib.check(self.lib.nmpc_eval_batch(self._h, B, p.data_ptr(), w.data_ptr(), f.data_ptr(), g.data_ptr(), self._stream()), "nmpc_eval_batch")
         return f, g
 
-    def kkt_batch(self, p, w, lam_g, lam_x, obstacles=None, want_grad: bool = False):
+    def kkt_batch(self, p, w, lam_g, lam_x, obstacles=None, want_grad: bool = False, reference=None):
         """KKT residuals of (w, lam_g, lam_x) for B instances on the device (nmpc_kkt_batch): res [B, 6] = (stat, eq, ineq, bnd, compl, sign) as
         include/nmpc.h defines them, and with want_grad also grad_lag [B, n_var] = grad f + J' lam_g + lam_x.  The multipliers may be a solve's
-        (want_duals=True) or any others; obstacles as in solve_batch.  Works on every handle."""
+        (want_duals=True) or any others; obstacles as in solve_batch, reference (nmpc_kkt_batch_ref) as in eval_batch.  Works on every handle."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
@@ -274,6 +291,12 @@ class NmpcSolver:
         res = torch.empty((B, 6), dtype=torch.float64, device=self.device)
         grad = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device) if want_grad else None
         with torch.cuda.device(self.device):
+            if reference is not None:
+                rf = self._reference(reference, B)
+                _lib.check(self.lib.nmpc_kkt_batch_ref(self._h, B, p.data_ptr(), rf[0].data_ptr(), rf[1], ob[0].data_ptr() if ob is not None else None,
+                                                       ob[1] if ob is not None else 0, w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), res.data_ptr(),
+                                                       grad.data_ptr() if want_grad else None, self._stream()), "nmpc_kkt_batch_ref")
+                return (res, grad) if want_grad else res
             _lib.check(self.lib.nmpc_kkt_batch(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
                                                w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), res.data_ptr(), grad.data_ptr() if want_grad else None,
                                                self._stream()), "nmpc_kkt_batch")
