@@ -310,6 +310,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 
     // pair (i,j) of flat index q
     auto pair_ij = [&](int q, int &i, int &j) { pair_of<M_>(q, i, j); };      // loop-free (nmpc_solve_common.h): the while-loop form was a divergent loop, ~60 issue slots per call
+    // The first trip of a `for (it = tid; ..)` loop has loop-invariant indices: the compiler computes them (and the addresses they lead to) once at
+    // kernel entry and keeps them in registers across the whole iteration, the sweeps included.  The item loops below start from a lane index it
+    // cannot see through, so their index arithmetic stays inside them.  Without it the fused pass of phase A does not fit the budgets of the
+    // six-robot kernels (258 VGPRs with the heading bound, 12 B of scratch in the latency shapes; with it 241..252, no scratch); on its own ±0.
+    auto tid_local = [&]() { int t = tid; asm volatile("" : "+v"(t)); return t; };
 
     // ---- trig cache of the current iterate
     auto trig = [&]() {
@@ -336,7 +341,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double r = fabs(ht - st);
             t += r; mh = fmax(mh, r);
         };
-        for (int it = tid; it < N * M_; it += TPB) {
+        for (int it = tid_local(); it < N * M_; it += TPB) {
             int k = it / M_, i = it - k * M_;
             const int ox = k * NX + 3 * i, ou = k * NU + 2 * i;
             double x0 = X[ox] + a * DX[ox], x1 = X[ox + 1] + a * DX[ox + 1], x2 = X[ox + 2] + a * DX[ox + 2];
@@ -357,7 +362,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             ls.add(pr);
             pr = 1.0;
         }
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
@@ -381,7 +386,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double r = fabs(h - sv + tv);
             t += r; mh = fmax(mh, r);
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double px = X[oi] + a * DX[oi], py = X[oi + 1] + a * DX[oi + 1];
@@ -416,6 +421,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         if (i == 0) { gpack[(size_t)k * G::PACK + G::PK_T] = T; gpack[(size_t)k * G::PACK + G::PK_ZERO] = 0.0; }
     }
     for (int q = tid; q < 3 * NP; q += TPB) gpack[G::PK_E + q] = 0.0;     // stage 0 carries no pair rows
+    for (int i = tid; i < M_; i += TPB) {      // nor bound, pair or cost terms on its (pinned) states: the fused pass (A) writes the state entries of stages 1 .. N
+#pragma unroll
+        for (int d = 0; d < 3; d++) { gpack[G::PK_G + NU + 3 * i + d] = 0.0; gpack[G::PK_HD + NU + 3 * i + d] = 0.0; }
+        gpack[G::PK_HXY + i] = 0.0;
+    }
     if (!prs)                                                              // no pair rows at all: the E slots of every stage are zero
         for (int e = tid; e < (N - 1) * 3 * NP; e += TPB) gpack[(size_t)(1 + e / (3 * NPd)) * G::PACK + G::PK_E + e % (3 * NPd)] = 0.0;
     // ---- slacks and duals from the current primal point (also the barrier restart after a stall)
@@ -514,18 +524,32 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #ifdef NMPC_PROFILE
         double dbg_code = -1.0, dbg_v[4] = {0, 0, 0, 0};
 #endif
-        for (int it = tid; it < N * M_; it += TPB) {
+        // FZ (the plain phase of an instance without obstacle rows) also writes the stage packs (B0) here, with the CURRENT mu: same items, same
+        // loads.  An item is the state rows of stage k + 1 and the control rows of stage k, so its pack entries go to two stages.  Every pack value
+        // is the expression of stage_packs_a / _b below; the sums of A keep their terms and their order.  With obstacle rows the separate passes
+        // stay: fused, their terms shared quotients with A's sums and the compiler contracted other products into multiply-adds (not bit-identical).
+        auto opt_err = [&](auto fzc) {
+        constexpr bool FZ = decltype(fzc)::value;
+        for (int it = tid_local(); it < N * M_; it += TPB) {
             int k = it / M_, i = it - k * M_, kk = k + 1;
             const double *x = X + kk * NX;
             double r0 = LAM[kk * NX + 3 * i], r1 = LAM[kk * NX + 3 * i + 1], r2 = LAM[kk * NX + 3 * i + 2];
             lsum += fabs(r0) + fabs(r1) + fabs(r2);
+            double g0 = 0.0, g1 = 0.0, g2 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, hxy = 0.0;      // state entries of stage kk's pack (FZ)
+            double vn = 0.0, sk = 0.0, ck = 0.0, ln0 = 0.0, ln1 = 0.0;
             if (kk < N) {
                 const double *ln = LAM + (kk + 1) * NX + 3 * i;
                 double v = U[kk * NU + 2 * i];
-                double a = -T * v * SN[kk * M_ + i], b = T * v * CS[kk * M_ + i];
+                sk = SN[kk * M_ + i]; ck = CS[kk * M_ + i];
+                double a = -T * v * sk, b = T * v * ck;
                 r0 += 2 * P.q[0] * (x[3 * i] - XS[3 * i]) - ln[0];
                 r1 += 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]) - ln[1];
                 r2 += 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]) - (ln[2] + a * ln[0] + b * ln[1]);
+                if constexpr (FZ) {
+                    g0 = 2 * P.q[0] * (x[3 * i] - XS[3 * i]); g1 = 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]); g2 = 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]);
+                    h0 = 2 * P.q[0]; h1 = 2 * P.q[1]; h2 = 2 * P.q[2];
+                    vn = v; ln0 = ln[0]; ln1 = ln[1];
+                }
             }
             // Jx^T z : bounds, pairs (ascending partner), obstacles
             double j0, j1, j2 = 0.0;
@@ -536,22 +560,41 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 zsum += zl0 + zu0 + zl1 + zu1;
                 double p0 = (x[3 * i] + P.xymax) * zl0, p1 = (P.xymax - x[3 * i]) * zu0, p2 = (x[3 * i + 1] + P.xymax) * zl1, p3 = (P.xymax - x[3 * i + 1]) * zu1;
                 szmax = fmax(szmax, fmax(fmax(p0, p1), fmax(p2, p3))); szmin = fmin(szmin, fmin(fmin(p0, p1), fmin(p2, p3)));
+                double zl2 = 0.0, zu2 = 0.0;
                 if (THB) {
-                    double zl2 = ZXL[sb + 2], zu2 = ZXU[sb + 2];
+                    zl2 = ZXL[sb + 2]; zu2 = ZXU[sb + 2];
                     j2 = zl2 - zu2; zsum += zl2 + zu2;
                     double p4 = (x[3 * i + 2] + P.thmax) * zl2, p5 = (P.thmax - x[3 * i + 2]) * zu2;
                     szmax = fmax(szmax, fmax(p4, p5)); szmin = fmin(szmin, fmin(p4, p5));
+                }
+                if constexpr (FZ) {   // bounds: v = mu/s - sigma (h - s), sigma = z/s, lower row gradient +1, upper row -1
+                    auto bv = [&](double sv, double zv, double hv, double &hd) { double sg = qdiv(zv, sv); hd += sg; return qdiv(mu, sv) - sg * (hv - sv); };
+                    g0 -= bv(x[3 * i] + P.xymax, zl0, x[3 * i] + P.xymax, h0) - bv(P.xymax - x[3 * i], zu0, P.xymax - x[3 * i], h0);
+                    g1 -= bv(x[3 * i + 1] + P.xymax, zl1, x[3 * i + 1] + P.xymax, h1) - bv(P.xymax - x[3 * i + 1], zu1, P.xymax - x[3 * i + 1], h1);
+                    if (THB) g2 -= bv(x[3 * i + 2] + P.thmax, zl2, x[3 * i + 2] + P.thmax, h2) - bv(P.thmax - x[3 * i + 2], zu2, P.thmax - x[3 * i + 2], h2);
                 }
             }
             if (kk <= N - 1) {
                 const double xi = x[3 * i], yi = x[3 * i + 1];
                 if (prs) {       // partners in ascending order (p-th partner: j = p, or p + 1 from the own index on); their duals requested first
-                    double zq[MPN];
-                    static_for<0, M_ - 1>([&](auto pc) { constexpr int p = decltype(pc)::value; zq[p] = ZPp[kk * NP + pidx_any<M_>(i, p + (p >= i ? 1 : 0))]; });
+                    double zq[MPN], sq[MPN];
+                    static_for<0, M_ - 1>([&](auto pc) {
+                        constexpr int p = decltype(pc)::value;
+                        const int q = pidx_any<M_>(i, p + (p >= i ? 1 : 0));
+                        zq[p] = ZPp[kk * NP + q];
+                        if constexpr (FZ) sq[p] = SPp[kk * NP + q];
+                    });
                     static_for<0, M_ - 1>([&](auto pc) {
                         constexpr int p = decltype(pc)::value;
                         const int j = p + (p >= i ? 1 : 0);
                         j0 += 2 * (xi - x[3 * j]) * zq[p]; j1 += 2 * (yi - x[3 * j + 1]) * zq[p];
+                        if constexpr (FZ) {
+                            double dx = xi - x[3 * j], dy = yi - x[3 * j + 1];
+                            double sv = sq[p], zv = zq[p], sg, v;
+                            sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_pair(dx, dy, P.dmin2) - sv);
+                            g0 -= 2 * dx * v; g1 -= 2 * dy * v;
+                            h0 += 4 * sg * dx * dx - 2 * zv; hxy += 4 * sg * dx * dy; h1 += 4 * sg * dy * dy - 2 * zv;
+                        }
                     });
                 }
                 for (int o = 0; o < K; o++) {
@@ -559,6 +602,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     j0 += qdiv(dx, rr) * z; j1 += qdiv(dy, rr) * z;
                 }
             }
+            if constexpr (FZ) { if (kk < N) h2 += T * vn * (ln0 * ck + ln1 * sk); }
 #ifdef NMPC_PROFILE
             { double m3 = fmax(fabs(r0 - j0), fmax(fabs(r1 - j1), fabs(r2 - j2)));
               if (m3 > e_d) { dbg_code = 1000.0 * kk + 10.0 * i + (fabs(r0 - j0) == m3 ? 0 : (fabs(r1 - j1) == m3 ? 1 : 2)); dbg_v[0] = r0 - j0; dbg_v[1] = r1 - j1; dbg_v[2] = r2 - j2; dbg_v[3] = r2; } }
@@ -567,6 +611,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             // control rows of stage k
             const double *ln = LAM + (k + 1) * NX + 3 * i, *u = U + k * NU + 2 * i;
             double c = CS[it], s = SN[it];
+            const double sl0 = SUL[k * NU + 2 * i], su0 = SUU[k * NU + 2 * i], sl1 = SUL[k * NU + 2 * i + 1], su1 = SUU[k * NU + 2 * i + 1];
             double zl0 = ZUL[k * NU + 2 * i], zu0 = ZUU[k * NU + 2 * i], zl1 = ZUL[k * NU + 2 * i + 1], zu1 = ZUU[k * NU + 2 * i + 1];
             double rv = 2 * P.r[0] * u[0] - T * (c * ln[0] + s * ln[1]) - (zl0 - zu0);
             double rw = 2 * P.r[1] * u[1] - T * ln[2] - (zl1 - zu1);
@@ -575,20 +620,57 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #endif
             e_d = fmax(e_d, fmax(fabs(rv), fabs(rw)));
             zsum += zl0 + zu0 + zl1 + zu1;
-            double p0 = SUL[k * NU + 2 * i] * zl0, p1 = SUU[k * NU + 2 * i] * zu0, p2 = SUL[k * NU + 2 * i + 1] * zl1, p3 = SUU[k * NU + 2 * i + 1] * zu1;
+            double p0 = sl0 * zl0, p1 = su0 * zu0, p2 = sl1 * zl1, p3 = su1 * zu1;
             szmax = fmax(szmax, fmax(fmax(p0, p1), fmax(p2, p3))); szmin = fmin(szmin, fmin(fmin(p0, p1), fmin(p2, p3)));
+            if constexpr (FZ) {
+                const double *xk = X + k * NX;
+                double *pk = gpack + (size_t)k * G::PACK, *pn = gpack + (size_t)kk * G::PACK;
+                const double hvt = T * (ln[0] * s - ln[1] * c);
+                double pg[2], ph[2];
+#pragma unroll
+                for (int d = 0; d < 2; d++) {      // control gradient / diagonal
+                    double lo = d ? -P.wmax : -P.vmax, sl = d ? sl1 : sl0, su = d ? su1 : su0, zl = d ? zl1 : zl0, zu = d ? zu1 : zu0;
+                    double vl = qdiv(mu, sl) - qdiv(zl, sl) * ((u[d] - lo) - sl), vu = qdiv(mu, su) - qdiv(zu, su) * ((-lo - u[d]) - su);
+                    pg[d] = 2 * P.r[d] * u[d] - (vl - vu);
+                    ph[d] = 2 * P.r[d] + qdiv(zl, sl) + qdiv(zu, su);
+                }
+                const double d0 = defect_xy(x[3 * i], xk[3 * i], T * u[0], c), d1 = defect_xy(x[3 * i + 1], xk[3 * i + 1], T * u[0], s), d2 = defect_th(x[3 * i + 2], xk[3 * i + 2], T, u[1]);
+                const double cf0 = T * c, cf1_ = T * s, cf2 = -T * u[0] * s, cf3 = T * u[0] * c;
+                pk[G::PK_G + 2 * i] = pg[0]; pk[G::PK_G + 2 * i + 1] = pg[1];
+                pk[G::PK_HD + 2 * i] = ph[0]; pk[G::PK_HD + 2 * i + 1] = ph[1];
+                {   // coefficients of [B A] belonging to robot i that depend on the iterate: (v_i: x, y) = T cos, T sin; (theta_i: x, y) = -T v sin, T v cos
+                    double *cf = pk + G::PK_CF + 4 * i;
+                    cf[0] = cf0; cf[1] = cf1_; cf[2] = cf2; cf[3] = cf3;
+                }
+                pk[G::PK_C + 3 * i] = d0; pk[G::PK_C + 3 * i + 1] = d1; pk[G::PK_C + 3 * i + 2] = d2;
+                pk[G::PK_HVT + i] = hvt;
+                pn[G::PK_G + NU + 3 * i] = g0; pn[G::PK_G + NU + 3 * i + 1] = g1; pn[G::PK_G + NU + 3 * i + 2] = g2;
+                pn[G::PK_HD + NU + 3 * i] = h0; pn[G::PK_HD + NU + 3 * i + 1] = h1; pn[G::PK_HD + NU + 3 * i + 2] = h2;
+                pn[G::PK_HXY + i] = hxy;
+            }
         }
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
-            double zv = ZPp[NP + it], pz = SPp[NP + it] * zv;
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
+            double zv = ZPp[NP + it], sv = SPp[NP + it], pz = sv * zv;
             zsum += zv; szmax = fmax(szmax, pz); szmin = fmin(szmin, pz);
+            if constexpr (FZ) {      // pair block E_ij = 4 sigma dp dp^T - 2 z I of the same (stage, pair): it does not depend on mu
+                int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
+                pair_ij(q, i, j);
+                double dx = X[k * NX + 3 * i] - X[k * NX + 3 * j], dy = X[k * NX + 3 * i + 1] - X[k * NX + 3 * j + 1];
+                double zz = zv, sg = qdiv(zz, sv);
+                double *pk = gpack + (size_t)k * G::PACK + G::PK_E + 3 * q;
+                pk[0] = -(4 * sg * dx * dx - 2 * zz); pk[1] = -(4 * sg * dx * dy); pk[2] = -(4 * sg * dy * dy - 2 * zz);
+            }
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        };
+        const bool fuse_packs = !el && K == 0;      // wave-uniform
+        if (fuse_packs) opt_err(std::true_type{}); else opt_err(std::false_type{});
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             double zv = ZO[MK + it], pz = SO[MK + it] * zv;
             zsum += zv; szmax = fmax(szmax, pz); szmin = fmin(szmin, pz);
         }
         if (el) {       // elastic phase: the products t (rho - z) of the elastic variables with their duals
-            for (int it = tid; it < (N - 1) * NPA; it += TPB) { const double pt = TPp[NP + it] * (rho - ZPp[NP + it]); szmax = fmax(szmax, pt); szmin = fmin(szmin, pt); }
-            for (int it = tid; it < (N - 1) * MK; it += TPB) { const double pt = TOb[MK + it] * (rho - ZO[MK + it]); szmax = fmax(szmax, pt); szmin = fmin(szmin, pt); }
+            for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) { const double pt = TPp[NP + it] * (rho - ZPp[NP + it]); szmax = fmax(szmax, pt); szmin = fmin(szmin, pt); }
+            for (int it = tid_local(); it < (N - 1) * MK; it += TPB) { const double pt = TOb[MK + it] * (rho - ZO[MK + it]); szmax = fmax(szmax, pt); szmin = fmin(szmin, pt); }
         }
 #ifdef NMPC_PROFILE
         { double my = e_d; double gm = wmax<TPB>(e_d, RED);
@@ -609,8 +691,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             status = NMPC_STATUS_CONVERGED;
             if (el) {       // the penalty problem's solution solves the NLP only if every elastic variable has closed
                 double tmax = 0.0;
-                for (int it = tid; it < (N - 1) * NPA; it += TPB) tmax = fmax(tmax, TPp[NP + it]);
-                for (int it = tid; it < (N - 1) * MK; it += TPB) tmax = fmax(tmax, TOb[MK + it]);
+                for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) tmax = fmax(tmax, TPp[NP + it]);
+                for (int it = tid_local(); it < (N - 1) * MK; it += TPB) tmax = fmax(tmax, TOb[MK + it]);
                 if (wmax<TPB>(tmax, RED) > NMPC_X0_TOL) status = NMPC_STATUS_STALLED;
             }
             break;
@@ -618,6 +700,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         if (iter >= P.max_iter) { status = NMPC_STATUS_MAX_ITER; break; }
         if (n_cold < NMPC_COLD_RETRIES && iter - it_base >= NMPC_COLD_RETRY_ITERS) { cold_retry(); break; }
         const double mu_min = P.tol / 10.0;
+        const double mu_packs = mu;      // the barrier parameter the fused pass wrote the stage packs with
         for (;;) {
             double cm = fmax(fabs(szmax - mu), fabs(szmin - mu));
             double Emu = fmax(fmax(e_d / s_d, e_c), fmax(e_h, cm / s_c));
@@ -629,9 +712,9 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 
         // ============ B0. stage packs: everything of stage k that does not depend on the cost-to-go
         // (a) per (stage, robot): x-gradient, diagonal additions, cross terms, coefficients, defects
-        auto stage_packs = [&](auto elc) {
+        auto stage_packs_a = [&](auto elc) {
         constexpr bool EL = decltype(elc)::value;      // elastic phase: its own instantiation (the plain one is the code of rounds 1-3)
-        for (int it = tid; it < N1 * M_; it += TPB) {
+        for (int it = tid_local(); it < N1 * M_; it += TPB) {
             int k = it / M_, i = it - k * M_;
             const double *x = X + k * NX;
             double *pk = gpack + (size_t)k * G::PACK;          // k == N: terminal block reuses the pack layout
@@ -707,8 +790,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             pk[G::PK_HD + NU + 3 * i] = h0; pk[G::PK_HD + NU + 3 * i + 1] = h1; pk[G::PK_HD + NU + 3 * i + 2] = h2;
             pk[G::PK_HXY + i] = hxy;
         }
+        };
         // (b) pair blocks E_ij = 4 sigma dp dp^T - 2 z I per (stage, pair)
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        auto stage_packs_b = [&](auto elc) {
+        constexpr bool EL = decltype(elc)::value;
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             double dx = X[k * NX + 3 * i] - X[k * NX + 3 * j], dy = X[k * NX + 3 * i + 1] - X[k * NX + 3 * j + 1];
@@ -719,7 +805,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             pk[0] = -(4 * sg * dx * dx - 2 * zz); pk[1] = -(4 * sg * dx * dy); pk[2] = -(4 * sg * dy * dy - 2 * zz);
         }
         };
-        if (el) stage_packs(std::true_type{}); else stage_packs(std::false_type{});
+        // fused: the packs were written by A; their mu-dependent part (a) again where the monotone update moved mu (a wave-uniform test)
+        if (el) { stage_packs_a(std::true_type{}); stage_packs_b(std::true_type{}); }
+        else if (!fuse_packs) { stage_packs_a(std::false_type{}); stage_packs_b(std::false_type{}); }
+        else if (mu != mu_packs) stage_packs_a(std::false_type{});
         __syncthreads();
         PROF_T(2);
 
@@ -1310,18 +1399,18 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             dphi_b += qdiv(ds, sv) + qdiv(dt, tv) - qdiv(rho, mu) * dt;      // -mu dphi_b = -mu (ds/s + dt/t) + rho dt: the penalty's part rides along (no second accumulator)
             return zv + dz;
         };
-        for (int e = tid; e < N * NU; e += TPB) {
+        for (int e = tid_local(); e < N * NU; e += TPB) {
             int c = e % NU;
             double lo = lbu(c), u = U[e], du = DU[e], sl = SUL[e], su = SUU[e];
             fb(sl, ZUL[e], du + ((u - lo) - sl)); fb(su, ZUU[e], -du + ((-lo - u) - su));
         }
-        for (int e = tid; e < N * NXB; e += TPB) {
+        for (int e = tid_local(); e < N * NXB; e += TPB) {
             int k = 1 + e / NXB, s = e - (k - 1) * NXB;
             double v = X[k * NX + bst(s)], dv = DX[k * NX + bst(s)], b = bvl(s), sl = v + b, su = b - v;
             fb(sl, ZXL[k * NXB + s], dv + ((v + b) - sl)); fb(su, ZXU[k * NXB + s], -dv + ((b - v) - su));
         }
         if (!el) {
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
@@ -1329,7 +1418,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double ds = ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv);
             mult_max = fmax(mult_max, fabs(fb(sv, ZPp[k * NP + q], ds)));
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e];
@@ -1337,14 +1426,14 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             mult_max = fmax(mult_max, fabs(fb(sv, ZO[k * MK + e], ds)));
         }
         } else {        // elastic phase: the same two loops over elastic rows
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
             double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1];
             mult_max = fmax(mult_max, fabs(fbe(SPp[k * NP + q], ZPp[k * NP + q], TPp[k * NP + q], h_pair(ex, ey, P.dmin2), jd_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1]))));
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey);
@@ -1357,7 +1446,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         //   lam+_k = A_k^T lam+_{k+1} - (grad f_k + W_k dx_k + W_xu du_k) + Jx_k^T (z + dz)_k
         auto multiplier_residuals = [&](auto elc) {
         constexpr bool EL = decltype(elc)::value;
-        for (int it = tid; it < N * M_; it += TPB) {
+        for (int it = tid_local(); it < N * M_; it += TPB) {
             int k = 1 + it / M_, i = it - (k - 1) * M_;
             const double *x = X + k * NX, *dx = DX + k * NX;
             double l0, l1, l2 = 0.0;
@@ -1446,7 +1535,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         // ============ E. l1 merit backtracking line search; (f, sum log s, theta) of the current point are carried
         double dphi = 0.0;
 #if NMPC_FUSE_DPHI
-        for (int it = tid; it < N * M_; it += TPB) {      // objective part only: the barrier part was summed by the step-length pass (D)
+        for (int it = tid_local(); it < N * M_; it += TPB) {      // objective part only: the barrier part was summed by the step-length pass (D)
             int k = it / M_, i = it - k * M_;
             if (k >= 1) {
 #pragma unroll
@@ -1457,7 +1546,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         }
         dphi -= mu * dphi_b;
 #else
-        for (int it = tid; it < N1 * M_; it += TPB) {
+        for (int it = tid_local(); it < N1 * M_; it += TPB) {
             int k = it / M_, i = it - k * M_;
             if (k >= 1 && k < N) {
 #pragma unroll
@@ -1482,7 +1571,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         }
 #endif
 #if !NMPC_FUSE_DPHI
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
@@ -1490,7 +1579,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double ds = ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv);
             dphi -= mu * ds / sv;
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e];
@@ -1557,13 +1646,13 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double z = zv + a_d * dz;
             return fmin(fmax(z, qdiv(1e-10 * mu, snew)), fmin(qdiv(1e10 * mu, snew), rho - qdiv(1e-10 * mu, tnew)));
         };
-        for (int e = tid; e < N * NU; e += TPB) {
+        for (int e = tid_local(); e < N * NU; e += TPB) {
             int c = e % NU;
             double lo = lbu(c), u = U[e], du = DU[e], sl = SUL[e], su = SUU[e], sn;
             ZUL[e] = zup(sl, ZUL[e], du + ((u - lo) - sl), sn); SUL[e] = sn;
             ZUU[e] = zup(su, ZUU[e], -du + ((-lo - u) - su), sn); SUU[e] = sn;
         }
-        for (int e = tid; e < N * NXB; e += TPB) {
+        for (int e = tid_local(); e < N * NXB; e += TPB) {
             int k = 1 + e / NXB, s = e - (k - 1) * NXB;
             const int es = k * NXB + s;
             double v = X[k * NX + bst(s)], dv = DX[k * NX + bst(s)], b = bvl(s), sl = v + b, su = b - v, sn;
@@ -1571,7 +1660,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             ZXU[es] = zup(su, ZXU[es], -dv + ((b - v) - su), sn);
         }
         if (!el) {
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
@@ -1580,7 +1669,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             ZPp[k * NP + q] = zup(sv, ZPp[k * NP + q], ds, sn);
             SPp[k * NP + q] = sn;
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e], sn;
@@ -1589,7 +1678,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             SO[k * MK + e] = sn;
         }
         } else {        // elastic phase
-        for (int it = tid; it < (N - 1) * NPA; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
             pair_ij(q, i, j);
             const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
@@ -1597,7 +1686,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             ZPp[k * NP + q] = zupe(SPp[k * NP + q], ZPp[k * NP + q], TPp[k * NP + q], h_pair(ex, ey, P.dmin2), jd_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1]), sn, tn);
             SPp[k * NP + q] = sn; TPp[k * NP + q] = tn;
         }
-        for (int it = tid; it < (N - 1) * MK; it += TPB) {
+        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
             int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
             const int oi = k * NX + 3 * i;
             double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sn, tn;
@@ -1606,8 +1695,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         }
         }
         __syncthreads();
-        for (int e = tid; e < N1 * NX; e += TPB) { X[e] += alpha * DX[e]; if (e >= NX) LAM[e] += alpha * (RV[e] - LAM[e]); }
-        for (int e = tid; e < N * NU; e += TPB) U[e] += alpha * DU[e];
+        for (int e = tid_local(); e < N1 * NX; e += TPB) { X[e] += alpha * DX[e]; if (e >= NX) LAM[e] += alpha * (RV[e] - LAM[e]); }
+        for (int e = tid_local(); e < N * NU; e += TPB) U[e] += alpha * DU[e];
         __syncthreads();
         trig();
         __syncthreads();
