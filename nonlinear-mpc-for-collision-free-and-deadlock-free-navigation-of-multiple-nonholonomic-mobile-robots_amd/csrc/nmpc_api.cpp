@@ -111,12 +111,9 @@ static void fill_params(const nmpc_config_t *c, nmpc::KParams *P)
     P->oCKP = take((int64_t)((N - 1) / NMPC_CKPT_EVERY + 1) * (nx * nx + nx));      // saved cost-to-go of the backward sweep (partial re-factorisation)
     P->stride = o;
     nmpc::lds_kernel_workspace(*P, m, &P->oPACK, &P->oKT, &P->stride2);
-    {   // slack / dual arrays of the column kernel: pair, obstacle, control-bound (slacks + duals) and state-bound (duals) rows
-        const int64_t N1 = N + 1, NPd = m * (m - 1) / 2, MK = m * K;
-        const int64_t dual = 2 * N1 * NPd + 2 * N1 * MK + 4 * (int64_t)N * nu + 2 * N1 * P->nxb;
-        P->oDUAL = P->stride2;
-        P->stride2 += (dual + 15) / 16 * 16;
-    }
+    // slack / dual arrays of the column kernel: pair, obstacle, control-bound (slacks + duals) and state-bound (duals) rows
+    P->oDUAL = P->stride2;
+    P->stride2 += (nmpc::col_dual_doubles(*P, m) + 15) / 16 * 16;
     {   // cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep (partial re-factorisation after a rejected pivot): the column
         // kernel stores its registers lane by lane, (3m + 1) x 64 doubles per slot; the element-per-lane kernel its [P | p] (smaller)
         const int64_t slots = (N - 1) / NMPC_CKPT_EVERY + 1;

@@ -88,6 +88,7 @@ hipError_t launch_solve_col(const KParams &P, const SolveVariant &v, int B, cons
 size_t lds_kernel_bytes(const KParams &P, int m);                 // the element-per-lane kernel's throughput shape
 size_t col_kernel_bytes(const KParams &P, int m, int shape);      // = select_solve_col(..).lds
 void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride);
+int64_t col_dual_doubles(const KParams &P, int m);                // column kernel: doubles of one instance's slack / dual block (at oDUAL)
 hipError_t launch_eval(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
 // KKT residuals of (w, lam_g, lam_x): res [B][6] = (stat, eq, ineq, bnd, compl, sign), grad_lag [B][nvar] or nullptr (include/nmpc.h, nmpc_kkt_batch)
 hipError_t launch_kkt(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,

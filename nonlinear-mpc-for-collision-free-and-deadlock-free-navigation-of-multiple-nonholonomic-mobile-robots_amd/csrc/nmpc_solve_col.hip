@@ -38,9 +38,6 @@ __device__ __forceinline__ double lane_read(double v, int lane)      // uniform 
 #ifndef NMPC_FW_PD
 #define NMPC_FW_PD ((M_ <= 6) ? 2 : 1)         // stages the forward sweep requests its rows ahead.  The rows come from L2 and the ring costs registers: with the spills of the earlier builds 1 was best (1 -> 198.5 k, 2 -> 194 k, 3 -> 191 k, 4 -> 176 k solves/s); on the spill-free build (A/B, one session) 2: six robots +1.3..2.5 %, B=16384 +1 %, two robots +2 %, 3: -22 % (the ring is spilled); ten robots 2: -1.6 %, stays 1
 #endif
-#ifndef NMPC_FW_FAKE
-#define NMPC_FW_FAKE 0       // development: 1 = the forward sweep re-reads stage 0's rows (wrong results; separates compute from memory time)
-#endif
 #ifndef NMPC_COL_DPP
 #define NMPC_COL_DPP 1
 #endif
@@ -58,9 +55,6 @@ __device__ __forceinline__ double lane_read(double v, int lane)      // uniform 
 #endif
 #ifndef NMPC_COL_DUMMY_ST
 #define NMPC_COL_DUMMY_ST (NU - 1)
-#endif
-#ifndef NMPC_FUSE_DPHI
-#define NMPC_FUSE_DPHI 1     // the barrier part of the merit function's directional derivative is summed by the step-length pass (same slots, same ds): one pass over the slack arrays less; A/B +0.7..1 %
 #endif
 #ifndef NMPC_COL_RP
 #define NMPC_COL_RP 1        // row-paired backward sweep for two to six robots (see the sweep); 0 keeps one row per register (A/B)
@@ -109,19 +103,12 @@ __device__ __forceinline__ double lane_gather(int src4, double v)     // v of la
     return __hiloint2double(__builtin_amdgcn_ds_bpermute(src4, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(src4, __double2loint(v)));
 }
 
-#ifndef NMPC_COL_SADDR
-#define NMPC_COL_SADDR 1
-#endif
 struct UArr {      // array of the instance's workspace (or of LDS): wave-uniform base, uniform element offset, 32-bit element index (see the kernel)
     double *b;
     int o;
     __device__ __forceinline__ double &operator[](int i) const
     {
-#if NMPC_COL_SADDR
         return *reinterpret_cast<double *>(reinterpret_cast<char *>(b) + (size_t)((uint32_t)(o + i) * 8u));
-#else
-        return b[o + i];
-#endif
     }
 };
 
@@ -137,6 +124,26 @@ template <int M_, int THB> struct GC : G2<M_, THB> {
     static constexpr int PACKC = ((PK_ZERO + 1 + 7) / 8) * 8;
     static constexpr int PACK = (PACKC < 64 && B::PACK >= 64) ? 64 : PACKC;      // two robots: one whole 64-lane slice, as before (no exec-masked staging)
     static_assert(PACK <= B::PACK, "the workspace is sized for G2's pack");
+};
+
+// Where one instance keeps its arrays, in doubles.  First the block every instantiation has in LDS, from the start of dynamic LDS: what the
+// serial sweeps touch (states, controls, multipliers, trig cache, step) plus one scratch region.  Then the block of the slacks and duals of the
+// inequality rows, which only the stage-parallel phases visit: it follows the first block in LDS, or starts at KParams::oDUAL in the
+// instance's workspace (see the kernel).  The kernel, its multiplier epilogue, the poison fill of debug builds, col_lds_bytes and the
+// workspace carve-up (col_dual_doubles) all take the layout from here.
+template <int M_, int THB> struct ColLayout {
+    using G = G2<M_, THB>;
+    static constexpr int RG = G::KTS > G::PACK ? G::KTS : G::PACK;      // least size of the scratch region: a staged stage factor or pack (sized, like the workspace, for G2's pack)
+    int X, U, LAM, SN, CS, DX, DU, RV, XS, RED, end;                    // [N1*NX] [N*NU] [N1*NX] [N*M] [N*M] [N1*NX] [N*NU] [max(N1*NX, RG)] [NX] [8]
+    int SPp, ZPp, SO, ZO, ZUL, ZUU, ZXL, ZXU, SUL, SUU, dual;           // [N1*NP] x 2, [N1*MK] x 2, [N*NU] x 2, [N1*NXB] x 2, [N*NU] x 2; dual: the block's length
+    __host__ __device__ ColLayout(int N, int K)
+    {
+        const int N1 = N + 1, MK = M_ * K;
+        X = 0; U = X + N1 * G::NX; LAM = U + N * G::NU; SN = LAM + N1 * G::NX; CS = SN + N * M_; DX = CS + N * M_; DU = DX + N1 * G::NX; RV = DU + N * G::NU;
+        XS = RV + ((N1 * G::NX > RG) ? N1 * G::NX : RG); RED = XS + G::NX; end = RED + 8;
+        SPp = 0; ZPp = SPp + N1 * G::NP; SO = ZPp + N1 * G::NP; ZO = SO + N1 * MK; ZUL = ZO + N1 * MK; ZUU = ZUL + N * G::NU; ZXL = ZUU + N * G::NU;
+        ZXU = ZXL + N1 * G::NXB; SUL = ZXU + N1 * G::NXB; SUU = SUL + N * G::NU; dual = SUU + N * G::NU;
+    }
 };
 
 // TPBK: threads per instance.  64 = the throughput shape (one wavefront per instance).  128 (256) = the LATENCY shape: a second wavefront (three more) shares
@@ -178,42 +185,41 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     // slacks and duals of the inequality rows are only ever visited by the stage-parallel phases (coalesced, each lane its own
     // items) and live in the instance's workspace in HBM/L2 — that is what lets two instances share a SIMD (<= 20 KB of LDS each)
     extern __shared__ double sm[];
-    // (the epilogue that writes the multipliers locates X, U, LAM, SN, CS, XS and the dual arrays a second time by this carve-up: change both)
-    double *X = sm;                       // [N1*NX]
-    double *U = X + N1 * NX;              // [N*NU]
-    double *LAM = U + N * NU;             // [N1*NX]   lam[k] pairs with defect c_{k-1}
-    double *SN = LAM + N1 * NX;           // [N*M]
-    double *CS = SN + N * M_;             // [N*M]
-    double *DX = CS + N * M_;             // [N1*NX]   step
-    double *DU = DX + N1 * NX;            // [N*NU]
-    double *RV = DU + N * NU;             // one region, two lives: PK [PACK] the staged pack of the backward sweep; RV [N1*NX] the residuals /
+    const ColLayout<M_, THB> L(N, K);
+    double *X = sm + L.X;                 // [N1*NX]
+    double *U = sm + L.U;                 // [N*NU]
+    double *LAM = sm + L.LAM;             // [N1*NX]   lam[k] pairs with defect c_{k-1}
+    double *SN = sm + L.SN;               // [N*M]
+    double *CS = sm + L.CS;               // [N*M]
+    double *DX = sm + L.DX;               // [N1*NX]   step
+    double *DU = sm + L.DU;               // [N*NU]
+    double *RV = sm + L.RV;               // one region, two lives: PK [PACK] the staged pack of the backward sweep; RV [N1*NX] the residuals /
     double *FS = RV, *PK = RV;            // QP multipliers of the adjoint recursion (FS [KTS]: staged stage factor, only the > 32-control forward path)
     constexpr int RG0 = G::KTS > G::PACK ? G::KTS : G::PACK;
-    double *XS = RV + ((N1 * NX > RG0) ? N1 * NX : RG0);   // [NX]
-    double *RED = XS + NX;                // [8]
+    static_assert(RG0 <= ColLayout<M_, THB>::RG, "the scratch region holds this kernel's staged pack");
+    double *XS = sm + L.XS;               // [NX]
+    double *RED = sm + L.RED;             // [8]
     // slacks and duals of the inequality rows: in the instance's workspace (HBM/L2) for the larger teams, whose LDS budget of
     // 20 KB (eight instances per CU) they would break; in LDS (DL = 1) for up to four robots when they fit that budget — there the
     // stage-parallel phases are most of an iteration and their loops make one trip, i.e. one exposed memory latency each
     // The arrays are (wave-uniform base, uniform offset) pairs indexed by a 32-bit element index: the byte offset is formed in 32 bits and zero-extended,
     // which the compiler addresses as scalar base + 32-bit vector offset (`global_load v, v_off, s[base:base+1]`) instead of a 64-bit vector address
-    // per access (two registers and two or three address instructions each).  NMPC_COL_SADDR = 0 keeps plain pointers (A/B).
-    double *gd = DLL ? (RED + 8) : (ws + inst * P.stride2 + P.oDUAL);
-    const int oZPp = N1 * NP, oSO = oZPp + N1 * NP, oZO = oSO + N1 * MK, oZUL = oZO + N1 * MK, oZUU = oZUL + N * NU, oZXL = oZUU + N * NU, oZXU = oZXL + N1 * NXB,
-              oSUL = oZXU + N1 * NXB, oSUU = oSUL + N * NU;
-    const UArr SPp{gd, 0};                // [N1*NP]   pair slacks
-    const UArr ZPp{gd, oZPp};             // [N1*NP]   pair duals
-    const UArr SO{gd, oSO};               // [N1*MK]   obstacle slacks
-    const UArr ZO{gd, oZO};               // [N1*MK]
-    const UArr ZUL{gd, oZUL};             // [N*NU]
-    const UArr ZUU{gd, oZUU};             // [N*NU]
-    const UArr ZXL{gd, oZXL};             // [N1*NXB]
-    const UArr ZXU{gd, oZXU};             // [N1*NXB]
-    const UArr SUL{gd, oSUL};             // [N*NU]    explicit slacks of the simple bounds
-    const UArr SUU{gd, oSUU};             // [N*NU]
+    // per access (two registers and two or three address instructions each).
+    double *gd = DLL ? (sm + L.end) : (ws + inst * P.stride2 + P.oDUAL);
+    const UArr SPp{gd, L.SPp};            // [N1*NP]   pair slacks
+    const UArr ZPp{gd, L.ZPp};            // [N1*NP]   pair duals
+    const UArr SO{gd, L.SO};              // [N1*MK]   obstacle slacks
+    const UArr ZO{gd, L.ZO};              // [N1*MK]
+    const UArr ZUL{gd, L.ZUL};            // [N*NU]
+    const UArr ZUU{gd, L.ZUU};            // [N*NU]
+    const UArr ZXL{gd, L.ZXL};            // [N1*NXB]
+    const UArr ZXU{gd, L.ZXU};            // [N1*NXB]
+    const UArr SUL{gd, L.SUL};            // [N*NU]    explicit slacks of the simple bounds
+    const UArr SUU{gd, L.SUU};            // [N*NU]
 
     // DL >= 2 (small teams, throughput shape): the stage factors — written by the backward sweep, read by the forward sweep — live in LDS as well, DL >= 3:
     // the stage packs too; otherwise both are in the instance's workspace (HBM/L2)
-    double *const dl_end = DLL ? gd + oSUU + N * NU : RED + 8;
+    double *const dl_end = sm + L.end + (DLL ? L.dual : 0);
     double *gkt = (DLL >= 2) ? dl_end : ws + inst * P.stride2 + P.oKT;       // [N][KTS]
     double *gpack = (DLL >= 3) ? dl_end + (size_t)N * G::KTS : ws + inst * P.stride2 + P.oPACK;   // [N][PACK] + terminal [2*NX]
     const UArr TPp{ws + inst * P.stride2 + P.oELAS, 0};           // [N1*NP]   elastic variables of the pair rows (elastic phase only; always in the workspace)
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #ifdef NMPC_POISON
     {   // debug build: every LDS word and the instance's HBM workspace start as NMPC_POISON, so that a read of anything this solve did not
         // write shows up as a parity failure instead of depending on what ran on the CU before
-        const int nl = (int)((DLL ? gd + oSUU + N * NU : RED + 8) - sm) + (DLL >= 2 ? N * G::KTS : 0) + (DLL >= 3 ? N1 * G::PACK : 0);
+        const int nl = L.end + (DLL ? L.dual : 0) + (DLL >= 2 ? N * G::KTS : 0) + (DLL >= 3 ? N1 * G::PACK : 0);
         for (int e = tid; e < nl; e += TPB) sm[e] = NMPC_POISON;
         for (size_t e = tid; e < (size_t)P.stride2; e += TPB) ws[inst * P.stride2 + e] = NMPC_POISON;
         __syncthreads();
@@ -277,19 +283,34 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     }
     __syncthreads();
 
+    // ---- the two row kinds with one item per (stage, ..): item `it` of the rows of stages k0, k0 + 1, .. -> stage k, slot within the stage
+    //      (pair q / robot-obstacle e, obstacle o) and where the positions it couples start in X: every loop over such rows decodes here
+    auto pair_row = [&](int it, int k0, int &k, int &q, int &oi, int &oj) {
+        int i, j;
+        k = k0 + it / NPd; q = it - (k - k0) * NP;
+        pair_of<M_>(q, i, j);      // loop-free (nmpc_solve_common.h): the while-loop form was a divergent loop, ~60 issue slots per call
+        oi = k * NX + 3 * i; oj = k * NX + 3 * j;
+    };
+    auto obs_row = [&](int it, int k0, int &k, int &e, int &o, int &oi) {
+        k = k0 + it / MK; e = it - (k - k0) * MK;
+        const int i = e / K;
+        o = e - i * K; oi = k * NX + 3 * i;
+    };
+
     // ---- stage-0 pair / obstacle rows act on the pinned state: feasibility pre-check
     {
         double bad = 0.0;
-        for (int q = tid; q < NPA; q += TPB) {
-            int i, j;
-            pair_of<M_>(q, i, j);
-            double dx = X[3 * i] - X[3 * j], dy = X[3 * i + 1] - X[3 * j + 1];
+        for (int it = tid; it < NPA; it += TPB) {
+            int k, q, oi, oj;
+            pair_row(it, 0, k, q, oi, oj);
+            double dx = X[oi] - X[oj], dy = X[oi + 1] - X[oj + 1];
             if (h_pair(dx, dy, P.dmin2) < -NMPC_X0_TOL) bad = 1.0;
         }
-        for (int e = tid; e < MK; e += TPB) {
-            int i = e / K, o = e - i * K;
-            double dx = X[3 * i] - OB(0, o, 0), dy = X[3 * i + 1] - OB(0, o, 1);
-            if (h_obs(r_obs(dx, dy), P.robdim, OB(0, o, 2), P.margin) < -NMPC_X0_TOL) bad = 1.0;
+        for (int it = tid; it < MK; it += TPB) {
+            int k, e, o, oi;
+            obs_row(it, 0, k, e, o, oi);
+            double dx = X[oi] - OB(k, o, 0), dy = X[oi + 1] - OB(k, o, 1);
+            if (h_obs(r_obs(dx, dy), P.robdim, OB(k, o, 2), P.margin) < -NMPC_X0_TOL) bad = 1.0;
         }
         bad = wmax<TPB>(bad, RED);
         if (bad > 0.0) {
@@ -308,8 +329,6 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         }
     }
 
-    // pair (i,j) of flat index q
-    auto pair_ij = [&](int q, int &i, int &j) { pair_of<M_>(q, i, j); };      // loop-free (nmpc_solve_common.h): the while-loop form was a divergent loop, ~60 issue slots per call
     // The first trip of a `for (it = tid; ..)` loop has loop-invariant indices: the compiler computes them (and the addresses they lead to) once at
     // kernel entry and keeps them in registers across the whole iteration, the sweeps included.  The item loops below start from a lane index it
     // cannot see through, so their index arithmetic stays inside them.  Without it the fused pass of phase A does not fit the budgets of the
@@ -363,9 +382,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             pr = 1.0;
         }
         for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
+            int k, q, oi, oj;
+            pair_row(it, 1, k, q, oi, oj);
             double dx = (X[oi] + a * DX[oi]) - (X[oj] + a * DX[oj]), dy = (X[oi + 1] + a * DX[oi + 1]) - (X[oj + 1] + a * DX[oj + 1]);
             double h = h_pair(dx, dy, P.dmin2);
             // trial slack: s + a ds, ds = J dx + (h0 - s)
@@ -387,8 +405,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             t += r; mh = fmax(mh, r);
         }
         for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
-            int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
-            const int oi = k * NX + 3 * i;
+            int k, e, o, oi;
+            obs_row(it, 1, k, e, o, oi);
             double px = X[oi] + a * DX[oi], py = X[oi + 1] + a * DX[oi + 1];
             double h = h_obs(r_obs(px - OB(k, o, 0), py - OB(k, o, 1)), P.robdim, OB(k, o, 2), P.margin);
             double sv = SO[k * MK + e], tv = 0.0;
@@ -431,10 +449,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     // ---- slacks and duals from the current primal point (also the barrier restart after a stall)
     auto init_barrier = [&]() {
         for (int it = tid; it < N1 * NP; it += TPB) {
-            int k = it / NPd, q = it - k * NP;
+            int k, q, oi, oj;
+            pair_row(it, 0, k, q, oi, oj);
             if (k >= 1 && k <= N - 1 && prs) {
-                int i, j; pair_ij(q, i, j);
-                double dx = X[k * NX + 3 * i] - X[k * NX + 3 * j], dy = X[k * NX + 3 * i + 1] - X[k * NX + 3 * j + 1];
+                double dx = X[oi] - X[oj], dy = X[oi + 1] - X[oj + 1];
                 const double hv = h_pair(dx, dy, P.dmin2);
                 if (el) {       // t absorbs the violation: s = h + t >= bp, 0 < z < rho
                     const double tv = fmax(bp, bp - hv), sv = hv + tv;
@@ -446,10 +464,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             } else { SPp[it] = 1.0; ZPp[it] = 0.0; }
         }
         for (int it = tid; it < N1 * MK; it += TPB) {
-            int k = it / MK, e = it - k * MK;
+            int k, e, o, oi;
+            obs_row(it, 0, k, e, o, oi);
             if (k >= 1 && k <= N - 1) {
-                int i = e / K, o = e - i * K;
-                double dx = X[k * NX + 3 * i] - OB(k, o, 0), dy = X[k * NX + 3 * i + 1] - OB(k, o, 1);
+                double dx = X[oi] - OB(k, o, 0), dy = X[oi + 1] - OB(k, o, 1);
                 const double hv = h_obs(r_obs(dx, dy), P.robdim, OB(k, o, 2), P.margin);
                 if (el) {
                     const double tv = fmax(bp, bp - hv), sv = hv + tv;
@@ -475,6 +493,71 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         }
         __syncthreads();
     };
+    // ---- terms of the stage packs (B0), each written ONCE.  The fused pass of phase A and stage_packs_a / _b call them with the values they
+    //      have loaded, so both paths form every pack entry by the same expression, operand for operand (their results are bit-identical).
+    struct XTerms { double g0 = 0.0, g1 = 0.0, g2 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, hxy = 0.0; };      // state entries of one (stage, robot): x-gradient, diagonal additions, xy cross term
+    auto pk_cost = [&](XTerms &t, const double *x, int i) __attribute__((always_inline)) {      // tracking cost (stages 1 .. N-1)
+        t.g0 = 2 * P.q[0] * (x[3 * i] - XS[3 * i]); t.g1 = 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]); t.g2 = 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]);
+        t.h0 = 2 * P.q[0]; t.h1 = 2 * P.q[1]; t.h2 = 2 * P.q[2];
+    };
+    // a bound row: v = mu/s - sigma (h - s), sigma = z/s, lower row gradient +1, upper row -1
+    auto bv = [&](double sv, double zv, double hv, double &hd) __attribute__((always_inline)) { double sg = qdiv(zv, sv); hd += sg; return qdiv(mu, sv) - sg * (hv - sv); };
+    auto pk_bounds = [&](XTerms &t, const double *x, int i, double zl0, double zu0, double zl1, double zu1, double zl2, double zu2) __attribute__((always_inline)) {
+        t.g0 -= bv(x[3 * i] + P.xymax, zl0, x[3 * i] + P.xymax, t.h0) - bv(P.xymax - x[3 * i], zu0, P.xymax - x[3 * i], t.h0);
+        t.g1 -= bv(x[3 * i + 1] + P.xymax, zl1, x[3 * i + 1] + P.xymax, t.h1) - bv(P.xymax - x[3 * i + 1], zu1, P.xymax - x[3 * i + 1], t.h1);
+        if (THB) t.g2 -= bv(x[3 * i + 2] + P.thmax, zl2, x[3 * i + 2] + P.thmax, t.h2) - bv(P.thmax - x[3 * i + 2], zu2, P.thmax - x[3 * i + 2], t.h2);
+    };
+    // a pair row with partner offset (dx, dy); tv: its elastic variable (elastic phase only)
+    auto pk_pair = [&](auto elc, XTerms &t, double dx, double dy, double sv, double zv, double tv) __attribute__((always_inline)) {
+        double sg, v;
+        if constexpr (decltype(elc)::value) el_sigma(mu, rho, sv, zv, tv, h_pair(dx, dy, P.dmin2), sg, v);
+        else { sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_pair(dx, dy, P.dmin2) - sv); }
+        t.g0 -= 2 * dx * v; t.g1 -= 2 * dy * v;
+        t.h0 += 4 * sg * dx * dx - 2 * zv; t.hxy += 4 * sg * dx * dy; t.h1 += 4 * sg * dy * dy - 2 * zv;
+    };
+    // an obstacle row with offset (dx, dy) from the obstacle's centre and its radius ro
+    auto pk_obs = [&](auto elc, XTerms &t, double dx, double dy, double ro, double sv, double zv, double tv) __attribute__((always_inline)) {
+        double rr = r_obs(dx, dy), n0 = qdiv(dx, rr), n1 = qdiv(dy, rr), sg, v, zz = qdiv(zv, rr);
+        if constexpr (decltype(elc)::value) el_sigma(mu, rho, sv, zv, tv, h_obs(rr, P.robdim, ro, P.margin), sg, v);
+        else { sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_obs(rr, P.robdim, ro, P.margin) - sv); }
+        t.g0 -= n0 * v; t.g1 -= n1 * v;
+        t.h0 += sg * n0 * n0 - zz * (1 - n0 * n0); t.hxy += sg * n0 * n1 + zz * n0 * n1; t.h1 += sg * n1 * n1 - zz * (1 - n1 * n1);
+    };
+    // second derivatives of the dynamics times the multipliers ln of the stage's defect: (theta, theta) and (v, theta)
+    auto pk_htt = [&](double v, double l0, double l1, double c, double s) __attribute__((always_inline)) { return T * v * (l0 * c + l1 * s); };
+    auto pk_hvt = [&](double l0, double l1, double c, double s) __attribute__((always_inline)) { return T * (l0 * s - l1 * c); };
+    // everything robot i's controls u of stage k bring to the stage's pack pk: gradient and diagonal of both control rows, the coefficients
+    // of [B A] that depend on the iterate, the defects against the next state xn, the (v, theta) cross term
+    auto pk_controls = [&](double *pk, int i, const double *u, const double *xk, const double *xn, const double *ln, double c, double s,
+                           double sl0, double su0, double sl1, double su1, double zl0, double zu0, double zl1, double zu1) __attribute__((always_inline)) {
+        auto row = [&](int d, double sl, double su, double zl, double zu) __attribute__((always_inline)) {
+            const double lo = d ? -P.wmax : -P.vmax;
+            double vl = qdiv(mu, sl) - qdiv(zl, sl) * ((u[d] - lo) - sl), vu = qdiv(mu, su) - qdiv(zu, su) * ((-lo - u[d]) - su);
+            pk[G::PK_G + 2 * i + d] = 2 * P.r[d] * u[d] - (vl - vu);
+            pk[G::PK_HD + 2 * i + d] = 2 * P.r[d] + qdiv(zl, sl) + qdiv(zu, su);
+        };
+        row(0, sl0, su0, zl0, zu0); row(1, sl1, su1, zl1, zu1);
+        double *cf = pk + G::PK_CF + 4 * i;      // (v_i: x, y) = T cos, T sin; (theta_i: x, y) = -T v sin, T v cos
+        cf[0] = T * c; cf[1] = T * s; cf[2] = -T * u[0] * s; cf[3] = T * u[0] * c;
+        pk[G::PK_C + 3 * i] = defect_xy(xn[3 * i], xk[3 * i], T * u[0], c);
+        pk[G::PK_C + 3 * i + 1] = defect_xy(xn[3 * i + 1], xk[3 * i + 1], T * u[0], s);
+        pk[G::PK_C + 3 * i + 2] = defect_th(xn[3 * i + 2], xk[3 * i + 2], T, u[1]);
+        pk[G::PK_HVT + i] = pk_hvt(ln[0], ln[1], c, s);
+    };
+    auto pk_states = [&](double *pk, int i, const XTerms &t) __attribute__((always_inline)) {
+        pk[G::PK_G + NU + 3 * i] = t.g0; pk[G::PK_G + NU + 3 * i + 1] = t.g1; pk[G::PK_G + NU + 3 * i + 2] = t.g2;
+        pk[G::PK_HD + NU + 3 * i] = t.h0; pk[G::PK_HD + NU + 3 * i + 1] = t.h1; pk[G::PK_HD + NU + 3 * i + 2] = t.h2;
+        pk[G::PK_HXY + i] = t.hxy;
+    };
+    // pair block E_ij = 4 sigma dp dp^T - 2 z I of (stage k, pair q), negated in the pack; the plain sigma = z / s does not depend on mu
+    auto pk_pair_block = [&](auto elc, int k, int q, double dx, double dy, double sv, double zz, double tv) __attribute__((always_inline)) {
+        double sg;
+        if constexpr (decltype(elc)::value) { double v_; el_sigma(mu, rho, sv, zz, tv, h_pair(dx, dy, P.dmin2), sg, v_); }
+        else sg = qdiv(zz, sv);
+        double *pk = gpack + (size_t)k * G::PACK + G::PK_E + 3 * q;
+        pk[0] = -(4 * sg * dx * dx - 2 * zz); pk[1] = -(4 * sg * dx * dy); pk[2] = -(4 * sg * dy * dy - 2 * zz);
+    };
+
     double f, lgs, th0, e_c, e_h;
     double delta_last, nu_pen, kkt = INFINITY;
     bool need_shift, restarting = false, cold = false;
@@ -526,7 +609,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #endif
         // FZ (the plain phase of an instance without obstacle rows) also writes the stage packs (B0) here, with the CURRENT mu: same items, same
         // loads.  An item is the state rows of stage k + 1 and the control rows of stage k, so its pack entries go to two stages.  Every pack value
-        // is the expression of stage_packs_a / _b below; the sums of A keep their terms and their order.  With obstacle rows the separate passes
+        // comes from the pk_* terms above, as in stage_packs_a / _b below; the sums of A keep their terms and their order.  With obstacle rows the separate passes
         // stay: fused, their terms shared quotients with A's sums and the compiler contracted other products into multiply-adds (not bit-identical).
         auto opt_err = [&](auto fzc) {
         constexpr bool FZ = decltype(fzc)::value;
@@ -535,7 +618,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             const double *x = X + kk * NX;
             double r0 = LAM[kk * NX + 3 * i], r1 = LAM[kk * NX + 3 * i + 1], r2 = LAM[kk * NX + 3 * i + 2];
             lsum += fabs(r0) + fabs(r1) + fabs(r2);
-            double g0 = 0.0, g1 = 0.0, g2 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, hxy = 0.0;      // state entries of stage kk's pack (FZ)
+            XTerms t;      // state entries of stage kk's pack (FZ)
             double vn = 0.0, sk = 0.0, ck = 0.0, ln0 = 0.0, ln1 = 0.0;
             if (kk < N) {
                 const double *ln = LAM + (kk + 1) * NX + 3 * i;
@@ -545,11 +628,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 r0 += 2 * P.q[0] * (x[3 * i] - XS[3 * i]) - ln[0];
                 r1 += 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]) - ln[1];
                 r2 += 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]) - (ln[2] + a * ln[0] + b * ln[1]);
-                if constexpr (FZ) {
-                    g0 = 2 * P.q[0] * (x[3 * i] - XS[3 * i]); g1 = 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]); g2 = 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]);
-                    h0 = 2 * P.q[0]; h1 = 2 * P.q[1]; h2 = 2 * P.q[2];
-                    vn = v; ln0 = ln[0]; ln1 = ln[1];
-                }
+                if constexpr (FZ) { pk_cost(t, x, i); vn = v; ln0 = ln[0]; ln1 = ln[1]; }
             }
             // Jx^T z : bounds, pairs (ascending partner), obstacles
             double j0, j1, j2 = 0.0;
@@ -567,12 +646,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     double p4 = (x[3 * i + 2] + P.thmax) * zl2, p5 = (P.thmax - x[3 * i + 2]) * zu2;
                     szmax = fmax(szmax, fmax(p4, p5)); szmin = fmin(szmin, fmin(p4, p5));
                 }
-                if constexpr (FZ) {   // bounds: v = mu/s - sigma (h - s), sigma = z/s, lower row gradient +1, upper row -1
-                    auto bv = [&](double sv, double zv, double hv, double &hd) { double sg = qdiv(zv, sv); hd += sg; return qdiv(mu, sv) - sg * (hv - sv); };
-                    g0 -= bv(x[3 * i] + P.xymax, zl0, x[3 * i] + P.xymax, h0) - bv(P.xymax - x[3 * i], zu0, P.xymax - x[3 * i], h0);
-                    g1 -= bv(x[3 * i + 1] + P.xymax, zl1, x[3 * i + 1] + P.xymax, h1) - bv(P.xymax - x[3 * i + 1], zu1, P.xymax - x[3 * i + 1], h1);
-                    if (THB) g2 -= bv(x[3 * i + 2] + P.thmax, zl2, x[3 * i + 2] + P.thmax, h2) - bv(P.thmax - x[3 * i + 2], zu2, P.thmax - x[3 * i + 2], h2);
-                }
+                if constexpr (FZ) pk_bounds(t, x, i, zl0, zu0, zl1, zu1, zl2, zu2);
             }
             if (kk <= N - 1) {
                 const double xi = x[3 * i], yi = x[3 * i + 1];
@@ -588,13 +662,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                         constexpr int p = decltype(pc)::value;
                         const int j = p + (p >= i ? 1 : 0);
                         j0 += 2 * (xi - x[3 * j]) * zq[p]; j1 += 2 * (yi - x[3 * j + 1]) * zq[p];
-                        if constexpr (FZ) {
-                            double dx = xi - x[3 * j], dy = yi - x[3 * j + 1];
-                            double sv = sq[p], zv = zq[p], sg, v;
-                            sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_pair(dx, dy, P.dmin2) - sv);
-                            g0 -= 2 * dx * v; g1 -= 2 * dy * v;
-                            h0 += 4 * sg * dx * dx - 2 * zv; hxy += 4 * sg * dx * dy; h1 += 4 * sg * dy * dy - 2 * zv;
-                        }
+                        if constexpr (FZ) pk_pair(std::false_type{}, t, xi - x[3 * j], yi - x[3 * j + 1], sq[p], zq[p], 0.0);
                     });
                 }
                 for (int o = 0; o < K; o++) {
@@ -602,7 +670,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     j0 += qdiv(dx, rr) * z; j1 += qdiv(dy, rr) * z;
                 }
             }
-            if constexpr (FZ) { if (kk < N) h2 += T * vn * (ln0 * ck + ln1 * sk); }
+            if constexpr (FZ) { if (kk < N) t.h2 += pk_htt(vn, ln0, ln1, ck, sk); }
 #ifdef NMPC_PROFILE
             { double m3 = fmax(fabs(r0 - j0), fmax(fabs(r1 - j1), fabs(r2 - j2)));
               if (m3 > e_d) { dbg_code = 1000.0 * kk + 10.0 * i + (fabs(r0 - j0) == m3 ? 0 : (fabs(r1 - j1) == m3 ? 1 : 2)); dbg_v[0] = r0 - j0; dbg_v[1] = r1 - j1; dbg_v[2] = r2 - j2; dbg_v[3] = r2; } }
@@ -623,42 +691,17 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double p0 = sl0 * zl0, p1 = su0 * zu0, p2 = sl1 * zl1, p3 = su1 * zu1;
             szmax = fmax(szmax, fmax(fmax(p0, p1), fmax(p2, p3))); szmin = fmin(szmin, fmin(fmin(p0, p1), fmin(p2, p3)));
             if constexpr (FZ) {
-                const double *xk = X + k * NX;
-                double *pk = gpack + (size_t)k * G::PACK, *pn = gpack + (size_t)kk * G::PACK;
-                const double hvt = T * (ln[0] * s - ln[1] * c);
-                double pg[2], ph[2];
-#pragma unroll
-                for (int d = 0; d < 2; d++) {      // control gradient / diagonal
-                    double lo = d ? -P.wmax : -P.vmax, sl = d ? sl1 : sl0, su = d ? su1 : su0, zl = d ? zl1 : zl0, zu = d ? zu1 : zu0;
-                    double vl = qdiv(mu, sl) - qdiv(zl, sl) * ((u[d] - lo) - sl), vu = qdiv(mu, su) - qdiv(zu, su) * ((-lo - u[d]) - su);
-                    pg[d] = 2 * P.r[d] * u[d] - (vl - vu);
-                    ph[d] = 2 * P.r[d] + qdiv(zl, sl) + qdiv(zu, su);
-                }
-                const double d0 = defect_xy(x[3 * i], xk[3 * i], T * u[0], c), d1 = defect_xy(x[3 * i + 1], xk[3 * i + 1], T * u[0], s), d2 = defect_th(x[3 * i + 2], xk[3 * i + 2], T, u[1]);
-                const double cf0 = T * c, cf1_ = T * s, cf2 = -T * u[0] * s, cf3 = T * u[0] * c;
-                pk[G::PK_G + 2 * i] = pg[0]; pk[G::PK_G + 2 * i + 1] = pg[1];
-                pk[G::PK_HD + 2 * i] = ph[0]; pk[G::PK_HD + 2 * i + 1] = ph[1];
-                {   // coefficients of [B A] belonging to robot i that depend on the iterate: (v_i: x, y) = T cos, T sin; (theta_i: x, y) = -T v sin, T v cos
-                    double *cf = pk + G::PK_CF + 4 * i;
-                    cf[0] = cf0; cf[1] = cf1_; cf[2] = cf2; cf[3] = cf3;
-                }
-                pk[G::PK_C + 3 * i] = d0; pk[G::PK_C + 3 * i + 1] = d1; pk[G::PK_C + 3 * i + 2] = d2;
-                pk[G::PK_HVT + i] = hvt;
-                pn[G::PK_G + NU + 3 * i] = g0; pn[G::PK_G + NU + 3 * i + 1] = g1; pn[G::PK_G + NU + 3 * i + 2] = g2;
-                pn[G::PK_HD + NU + 3 * i] = h0; pn[G::PK_HD + NU + 3 * i + 1] = h1; pn[G::PK_HD + NU + 3 * i + 2] = h2;
-                pn[G::PK_HXY + i] = hxy;
+                pk_controls(gpack + (size_t)k * G::PACK, i, u, X + k * NX, x, ln, c, s, sl0, su0, sl1, su1, zl0, zu0, zl1, zu1);
+                pk_states(gpack + (size_t)kk * G::PACK, i, t);
             }
         }
         for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
             double zv = ZPp[NP + it], sv = SPp[NP + it], pz = sv * zv;
             zsum += zv; szmax = fmax(szmax, pz); szmin = fmin(szmin, pz);
-            if constexpr (FZ) {      // pair block E_ij = 4 sigma dp dp^T - 2 z I of the same (stage, pair): it does not depend on mu
-                int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-                pair_ij(q, i, j);
-                double dx = X[k * NX + 3 * i] - X[k * NX + 3 * j], dy = X[k * NX + 3 * i + 1] - X[k * NX + 3 * j + 1];
-                double zz = zv, sg = qdiv(zz, sv);
-                double *pk = gpack + (size_t)k * G::PACK + G::PK_E + 3 * q;
-                pk[0] = -(4 * sg * dx * dx - 2 * zz); pk[1] = -(4 * sg * dx * dy); pk[2] = -(4 * sg * dy * dy - 2 * zz);
+            if constexpr (FZ) {      // the pair block of the same (stage, pair)
+                int k, q, oi, oj;
+                pair_row(it, 1, k, q, oi, oj);
+                pk_pair_block(std::false_type{}, k, q, X[oi] - X[oj], X[oi + 1] - X[oj + 1], sv, zv, 0.0);
             }
         }
         };
@@ -718,19 +761,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             int k = it / M_, i = it - k * M_;
             const double *x = X + k * NX;
             double *pk = gpack + (size_t)k * G::PACK;          // k == N: terminal block reuses the pack layout
-            double g0 = 0.0, g1 = 0.0, g2 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, hxy = 0.0;
+            XTerms t;
             if (k >= 1) {
-                if (k < N) {
-                    g0 = 2 * P.q[0] * (x[3 * i] - XS[3 * i]); g1 = 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]); g2 = 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]);
-                    h0 = 2 * P.q[0]; h1 = 2 * P.q[1]; h2 = 2 * P.q[2];
-                }
+                if (k < N) pk_cost(t, x, i);
                 const int sb = k * NXB + (2 + THB) * i;
-                {   // bounds: v = mu/s - sigma (h - s), sigma = z/s, lower row gradient +1, upper row -1
-                    auto bv = [&](double sv, double zv, double hv, double &hd) { double sg = qdiv(zv, sv); hd += sg; return qdiv(mu, sv) - sg * (hv - sv); };
-                    g0 -= bv(x[3 * i] + P.xymax, ZXL[sb], x[3 * i] + P.xymax, h0) - bv(P.xymax - x[3 * i], ZXU[sb], P.xymax - x[3 * i], h0);
-                    g1 -= bv(x[3 * i + 1] + P.xymax, ZXL[sb + 1], x[3 * i + 1] + P.xymax, h1) - bv(P.xymax - x[3 * i + 1], ZXU[sb + 1], P.xymax - x[3 * i + 1], h1);
-                    if (THB) g2 -= bv(x[3 * i + 2] + P.thmax, ZXL[sb + 2], x[3 * i + 2] + P.thmax, h2) - bv(P.thmax - x[3 * i + 2], ZXU[sb + 2], P.thmax - x[3 * i + 2], h2);
-                }
+                pk_bounds(t, x, i, ZXL[sb], ZXU[sb], ZXL[sb + 1], ZXU[sb + 1], THB ? ZXL[sb + 2] : 0.0, THB ? ZXU[sb + 2] : 0.0);
                 if (k <= N - 1) {
                     const double xi = x[3 * i], yi = x[3 * i + 1];
                     if (prs) {
@@ -743,66 +778,38 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                         static_for<0, M_ - 1>([&](auto pc) {
                             constexpr int p = decltype(pc)::value;
                             const int j = p + (p >= i ? 1 : 0);
-                            double dx = xi - x[3 * j], dy = yi - x[3 * j + 1];
-                            double sv = sq[p], zv = zq[p], sg, v;
-                            if constexpr (EL) el_sigma(mu, rho, sv, zv, TPp[k * NP + pidx_any<M_>(i, j)], h_pair(dx, dy, P.dmin2), sg, v);
-                            else { sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_pair(dx, dy, P.dmin2) - sv); }
-                            g0 -= 2 * dx * v; g1 -= 2 * dy * v;
-                            h0 += 4 * sg * dx * dx - 2 * zv; hxy += 4 * sg * dx * dy; h1 += 4 * sg * dy * dy - 2 * zv;
+                            double tv = 0.0;
+                            if constexpr (EL) tv = TPp[k * NP + pidx_any<M_>(i, j)];
+                            pk_pair(elc, t, xi - x[3 * j], yi - x[3 * j + 1], sq[p], zq[p], tv);
                         });
                     }
                     for (int o = 0; o < K; o++) {
-                        double dx = xi - OB(k, o, 0), dy = yi - OB(k, o, 1), rr = r_obs(dx, dy), n0 = qdiv(dx, rr), n1 = qdiv(dy, rr);
-                        double sv = SO[k * MK + i * K + o], zv = ZO[k * MK + i * K + o], sg, v, zz = qdiv(zv, rr);
-                        if constexpr (EL) el_sigma(mu, rho, sv, zv, TOb[k * MK + i * K + o], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sg, v);
-                        else { sg = qdiv(zv, sv); v = qdiv(mu, sv) - sg * (h_obs(rr, P.robdim, OB(k, o, 2), P.margin) - sv); }
-                        g0 -= n0 * v; g1 -= n1 * v;
-                        h0 += sg * n0 * n0 - zz * (1 - n0 * n0); hxy += sg * n0 * n1 + zz * n0 * n1; h1 += sg * n1 * n1 - zz * (1 - n1 * n1);
+                        const int eo = k * MK + i * K + o;
+                        double tv = 0.0;
+                        if constexpr (EL) tv = TOb[eo];
+                        pk_obs(elc, t, xi - OB(k, o, 0), yi - OB(k, o, 1), OB(k, o, 2), SO[eo], ZO[eo], tv);
                     }
                 }
             }
-            double hvt = 0.0;
             if (k < N) {
                 const double *u = U + k * NU + 2 * i, *ln = LAM + (k + 1) * NX + 3 * i;
-                double c = CS[it], s = SN[it];
-                if (k >= 1) h2 += T * u[0] * (ln[0] * c + ln[1] * s);
-                hvt = T * (ln[0] * s - ln[1] * c);
-                // control gradient / diagonal
-#pragma unroll
-                for (int d = 0; d < 2; d++) {
-                    const int eu = k * NU + 2 * i + d;
-                    double lo = d ? -P.wmax : -P.vmax, sl = SUL[eu], su = SUU[eu], zl = ZUL[eu], zu = ZUU[eu];
-                    double vl = qdiv(mu, sl) - qdiv(zl, sl) * ((u[d] - lo) - sl), vu = qdiv(mu, su) - qdiv(zu, su) * ((-lo - u[d]) - su);
-                    pk[G::PK_G + 2 * i + d] = 2 * P.r[d] * u[d] - (vl - vu);
-                    pk[G::PK_HD + 2 * i + d] = 2 * P.r[d] + qdiv(zl, sl) + qdiv(zu, su);
-                }
-                {   // coefficients of [B A] belonging to robot i that depend on the iterate: (v_i: x, y) = T cos, T sin; (theta_i: x, y) = -T v sin, T v cos
-                    double *cf = pk + G::PK_CF + 4 * i;
-                    cf[0] = T * c; cf[1] = T * s; cf[2] = -T * u[0] * s; cf[3] = T * u[0] * c;
-                }
-                const double *xn = x + NX;
-                pk[G::PK_C + 3 * i] = defect_xy(xn[3 * i], x[3 * i], T * u[0], c);
-                pk[G::PK_C + 3 * i + 1] = defect_xy(xn[3 * i + 1], x[3 * i + 1], T * u[0], s);
-                pk[G::PK_C + 3 * i + 2] = defect_th(xn[3 * i + 2], x[3 * i + 2], T, u[1]);
-                pk[G::PK_HVT + i] = hvt;
+                const double c = CS[it], s = SN[it];
+                const int eu = k * NU + 2 * i;
+                if (k >= 1) t.h2 += pk_htt(u[0], ln[0], ln[1], c, s);
+                pk_controls(pk, i, u, x, x + NX, ln, c, s, SUL[eu], SUU[eu], SUL[eu + 1], SUU[eu + 1], ZUL[eu], ZUU[eu], ZUL[eu + 1], ZUU[eu + 1]);
             }
-            pk[G::PK_G + NU + 3 * i] = g0; pk[G::PK_G + NU + 3 * i + 1] = g1; pk[G::PK_G + NU + 3 * i + 2] = g2;
-            pk[G::PK_HD + NU + 3 * i] = h0; pk[G::PK_HD + NU + 3 * i + 1] = h1; pk[G::PK_HD + NU + 3 * i + 2] = h2;
-            pk[G::PK_HXY + i] = hxy;
+            pk_states(pk, i, t);
         }
         };
-        // (b) pair blocks E_ij = 4 sigma dp dp^T - 2 z I per (stage, pair)
+        // (b) pair blocks per (stage, pair)
         auto stage_packs_b = [&](auto elc) {
         constexpr bool EL = decltype(elc)::value;
         for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            double dx = X[k * NX + 3 * i] - X[k * NX + 3 * j], dy = X[k * NX + 3 * i + 1] - X[k * NX + 3 * j + 1];
-            double zz = ZPp[k * NP + q], sg;
-            if constexpr (EL) { double v_; el_sigma(mu, rho, SPp[k * NP + q], zz, TPp[k * NP + q], h_pair(dx, dy, P.dmin2), sg, v_); }
-            else sg = qdiv(zz, SPp[k * NP + q]);
-            double *pk = gpack + (size_t)k * G::PACK + G::PK_E + 3 * q;
-            pk[0] = -(4 * sg * dx * dx - 2 * zz); pk[1] = -(4 * sg * dx * dy); pk[2] = -(4 * sg * dy * dy - 2 * zz);
+            int k, q, oi, oj;
+            pair_row(it, 1, k, q, oi, oj);
+            double tv = 0.0;
+            if constexpr (EL) tv = TPp[k * NP + q];
+            pk_pair_block(elc, k, q, X[oi] - X[oj], X[oi + 1] - X[oj + 1], SPp[k * NP + q], ZPp[k * NP + q], tv);
         }
         };
         // fused: the packs were written by A; their mu-dependent part (a) again where the monotone update moved mu (a wave-uniform test)
@@ -1254,7 +1261,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 constexpr int d = decltype(dc)::value;
 #pragma unroll
                 for (int t = 0; t < CH; t++) {      // every lane loads (the lanes without a role read what lane 16 reads): no exec-masked regions
-                    const double2 v = rowp[(size_t)(NMPC_FW_FAKE ? 0 : k) * (G::KTS / 2) + t];
+                    const double2 v = rowp[(size_t)k * (G::KTS / 2) + t];
                     kq[d][2 * t] = v.x; kq[d][2 * t + 1] = v.y;
                 }
             };
@@ -1377,16 +1384,12 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 
         // ============ D. fraction to the boundary (IPOPT eq. 15) over all inequality slots (ds, dz recomputed)
         double a_p = 1.0, a_d = 1.0, mult_max = 0.0;   // mult_max: inf-norm of the QP multipliers of the rows that enter theta
-#if NMPC_FUSE_DPHI
         double dphi_b = 0.0;        // barrier part of the merit function's directional derivative, -mu sum ds / s: same slots, same ds (one pass less)
-#endif
         auto fb = [&](double sv, double zv, double ds) -> double {
             double dz = dz_of(mu, sv, zv, ds);
             if (ds < 0.0) a_p = fmin(a_p, qdiv(-tau * sv, ds));
             if (dz < 0.0) a_d = fmin(a_d, qdiv(-tau * zv, dz));
-#if NMPC_FUSE_DPHI
             dphi_b += qdiv(ds, sv);
-#endif
             return zv + dz;
         };
         auto fbe = [&](double sv, double zv, double tv, double hv, double jd) -> double {      // an elastic row: s, t >= 0, 0 < z < rho
@@ -1409,37 +1412,27 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double v = X[k * NX + bst(s)], dv = DX[k * NX + bst(s)], b = bvl(s), sl = v + b, su = b - v;
             fb(sl, ZXL[k * NXB + s], dv + ((v + b) - sl)); fb(su, ZXU[k * NXB + s], -dv + ((b - v) - su));
         }
-        if (!el) {
+        auto step_length_rows = [&](auto elc) {
+        constexpr bool EL = decltype(elc)::value;      // elastic phase: the same two loops over elastic rows
         for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
-            double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1], sv = SPp[k * NP + q];
-            double ds = ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv);
-            mult_max = fmax(mult_max, fabs(fb(sv, ZPp[k * NP + q], ds)));
+            int k, q, oi, oj;
+            pair_row(it, 1, k, q, oi, oj);
+            double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1], sv = SPp[k * NP + q], zn;
+            if constexpr (EL) zn = fbe(sv, ZPp[k * NP + q], TPp[k * NP + q], h_pair(ex, ey, P.dmin2), jd_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1]));
+            else zn = fb(sv, ZPp[k * NP + q], ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv));
+            mult_max = fmax(mult_max, fabs(zn));
         }
         for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
-            int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
-            const int oi = k * NX + 3 * i;
-            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e];
-            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
-            mult_max = fmax(mult_max, fabs(fb(sv, ZO[k * MK + e], ds)));
+            int k, e, o, oi;
+            obs_row(it, 1, k, e, o, oi);
+            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e], zn;
+            const double hv = h_obs(rr, P.robdim, OB(k, o, 2), P.margin);
+            if constexpr (EL) zn = fbe(sv, ZO[k * MK + e], TOb[k * MK + e], hv, jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]));
+            else zn = fb(sv, ZO[k * MK + e], ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], hv, sv));
+            mult_max = fmax(mult_max, fabs(zn));
         }
-        } else {        // elastic phase: the same two loops over elastic rows
-        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
-            double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1];
-            mult_max = fmax(mult_max, fabs(fbe(SPp[k * NP + q], ZPp[k * NP + q], TPp[k * NP + q], h_pair(ex, ey, P.dmin2), jd_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1]))));
-        }
-        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
-            int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
-            const int oi = k * NX + 3 * i;
-            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey);
-            mult_max = fmax(mult_max, fabs(fbe(SO[k * MK + e], ZO[k * MK + e], TOb[k * MK + e], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]))));
-        }
-        }
+        };
+        if (el) step_length_rows(std::true_type{}); else step_length_rows(std::false_type{});
         a_p = wmin<TPB>(a_p, RED); a_d = wmin<TPB>(a_d, RED);
         PROF_T(5);
         // ============ F. multipliers of the QP: stage-parallel residuals, then the robot-local adjoint recursion in registers
@@ -1505,7 +1498,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 l2 -= 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]) + 2 * P.q[2] * dx[3 * i + 2];
                 const double *ln = LAM + (k + 1) * NX + 3 * i;
                 double v = U[k * NU + 2 * i], c = CS[k * M_ + i], s = SN[k * M_ + i];
-                double htt = T * v * (ln[0] * c + ln[1] * s), hvt = T * (ln[0] * s - ln[1] * c);
+                double htt = pk_htt(v, ln[0], ln[1], c, s), hvt = pk_hvt(ln[0], ln[1], c, s);
                 l2 -= htt * dx[3 * i + 2] + hvt * DU[k * NU + 2 * i];
             }
             RV[k * NX + 3 * i] = l0; RV[k * NX + 3 * i + 1] = l1; RV[k * NX + 3 * i + 2] = l2;
@@ -1534,7 +1527,6 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 
         // ============ E. l1 merit backtracking line search; (f, sum log s, theta) of the current point are carried
         double dphi = 0.0;
-#if NMPC_FUSE_DPHI
         for (int it = tid_local(); it < N * M_; it += TPB) {      // objective part only: the barrier part was summed by the step-length pass (D)
             int k = it / M_, i = it - k * M_;
             if (k >= 1) {
@@ -1545,48 +1537,6 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             for (int d = 0; d < 2; d++) { const int eu = k * NU + 2 * i + d; dphi += 2 * P.r[d] * U[eu] * DU[eu]; }
         }
         dphi -= mu * dphi_b;
-#else
-        for (int it = tid_local(); it < N1 * M_; it += TPB) {
-            int k = it / M_, i = it - k * M_;
-            if (k >= 1 && k < N) {
-#pragma unroll
-                for (int d = 0; d < 3; d++) dphi += 2 * P.q[d] * (X[k * NX + 3 * i + d] - XS[3 * i + d]) * DX[k * NX + 3 * i + d];
-            }
-            if (k < N) {
-#pragma unroll
-                for (int d = 0; d < 2; d++) {
-                    const int eu = k * NU + 2 * i + d;
-                    double u = U[eu], du = DU[eu], lo = d ? -P.wmax : -P.vmax, sl = SUL[eu], su = SUU[eu];
-                    dphi += 2 * P.r[d] * u * du - mu * ((du + ((u - lo) - sl)) / sl + (-du + ((-lo - u) - su)) / su);
-                }
-            }
-            if (k >= 1) {
-#pragma unroll
-                for (int d = 0; d < 2 + THB; d++) {
-                    const int sb = k * NXB + (2 + THB) * i + d;
-                    double v = X[k * NX + 3 * i + d], dv = DX[k * NX + 3 * i + d], b = (d == 2) ? P.thmax : P.xymax, sl = v + b, su = b - v;
-                    dphi -= mu * ((dv + ((v + b) - sl)) / sl + (-dv + ((b - v) - su)) / su);
-                }
-            }
-        }
-#endif
-#if !NMPC_FUSE_DPHI
-        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
-            double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1], sv = SPp[k * NP + q];
-            double ds = ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv);
-            dphi -= mu * ds / sv;
-        }
-        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
-            int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
-            const int oi = k * NX + 3 * i;
-            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e];
-            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
-            dphi -= mu * ds / sv;
-        }
-#endif
         dphi = wsum<TPB>(dphi, RED);
         const double phi0 = f - mu * lgs;
         if (th0 > 0.0) {
@@ -1659,41 +1609,33 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             ZXL[es] = zup(sl, ZXL[es], dv + ((v + b) - sl), sn);
             ZXU[es] = zup(su, ZXU[es], -dv + ((b - v) - su), sn);
         }
-        if (!el) {
+        auto accept_rows = [&](auto elc) {
+        constexpr bool EL = decltype(elc)::value;
         for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
+            int k, q, oi, oj;
+            pair_row(it, 1, k, q, oi, oj);
             double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1], sv = SPp[k * NP + q], sn;
-            double ds = ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv);
-            ZPp[k * NP + q] = zup(sv, ZPp[k * NP + q], ds, sn);
+            if constexpr (EL) {
+                double tn;
+                ZPp[k * NP + q] = zupe(sv, ZPp[k * NP + q], TPp[k * NP + q], h_pair(ex, ey, P.dmin2), jd_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1]), sn, tn);
+                TPp[k * NP + q] = tn;
+            } else ZPp[k * NP + q] = zup(sv, ZPp[k * NP + q], ds_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1], P.dmin2, sv), sn);
             SPp[k * NP + q] = sn;
         }
         for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
-            int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
-            const int oi = k * NX + 3 * i;
+            int k, e, o, oi;
+            obs_row(it, 1, k, e, o, oi);
             double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sv = SO[k * MK + e], sn;
-            double ds = ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), sv);
-            ZO[k * MK + e] = zup(sv, ZO[k * MK + e], ds, sn);
+            const double hv = h_obs(rr, P.robdim, OB(k, o, 2), P.margin);
+            if constexpr (EL) {
+                double tn;
+                ZO[k * MK + e] = zupe(sv, ZO[k * MK + e], TOb[k * MK + e], hv, jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]), sn, tn);
+                TOb[k * MK + e] = tn;
+            } else ZO[k * MK + e] = zup(sv, ZO[k * MK + e], ds_obs(ex, ey, rr, DX[oi], DX[oi + 1], hv, sv), sn);
             SO[k * MK + e] = sn;
         }
-        } else {        // elastic phase
-        for (int it = tid_local(); it < (N - 1) * NPA; it += TPB) {
-            int k = 1 + it / NPd, q = it - (k - 1) * NP, i, j;
-            pair_ij(q, i, j);
-            const int oi = k * NX + 3 * i, oj = k * NX + 3 * j;
-            double ex = X[oi] - X[oj], ey = X[oi + 1] - X[oj + 1], sn, tn;
-            ZPp[k * NP + q] = zupe(SPp[k * NP + q], ZPp[k * NP + q], TPp[k * NP + q], h_pair(ex, ey, P.dmin2), jd_pair(ex, ey, DX[oi] - DX[oj], DX[oi + 1] - DX[oj + 1]), sn, tn);
-            SPp[k * NP + q] = sn; TPp[k * NP + q] = tn;
-        }
-        for (int it = tid_local(); it < (N - 1) * MK; it += TPB) {
-            int k = 1 + it / MK, e = it - (k - 1) * MK, i = e / K, o = e - i * K;
-            const int oi = k * NX + 3 * i;
-            double ex = X[oi] - OB(k, o, 0), ey = X[oi + 1] - OB(k, o, 1), rr = r_obs(ex, ey), sn, tn;
-            ZO[k * MK + e] = zupe(SO[k * MK + e], ZO[k * MK + e], TOb[k * MK + e], h_obs(rr, P.robdim, OB(k, o, 2), P.margin), jd_obs(ex, ey, rr, DX[oi], DX[oi + 1]), sn, tn);
-            SO[k * MK + e] = sn; TOb[k * MK + e] = tn;
-        }
-        }
+        };
+        if (el) accept_rows(std::true_type{}); else accept_rows(std::false_type{});
         __syncthreads();
         for (int e = tid_local(); e < N1 * NX; e += TPB) { X[e] += alpha * DX[e]; if (e >= NX) LAM[e] += alpha * (RV[e] - LAM[e]); }
         for (int e = tid_local(); e < N * NU; e += TPB) U[e] += alpha * DU[e];
@@ -1718,8 +1660,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     for (int e = tid; e < N1 * NX; e += TPB) wo[e] = X[e];
     for (int e = tid; e < N * NU; e += TPB) wo[(size_t)N1 * NX + e] = U[e];
     // ---- the multipliers of the returned point in CasADi's layout and sign (include/nmpc.h, nmpc_solve_batch_duals): L = f + lam_g' g + lam_x' w
-    //      + lam_p' p.  One wave-uniform test of the pointers, nothing on the plain path.  The block locates the instance's arrays AGAIN, by the
-    //      carve-up at the top of the kernel, from N and K passed through an empty asm: otherwise the compiler keeps the main loop's bases and
+    //      + lam_p' p.  One wave-uniform test of the pointers, nothing on the plain path.  The block locates the instance's arrays AGAIN, by a
+    //      second ColLayout made from N and K passed through an empty asm: otherwise the compiler keeps the main loop's bases and
     //      offsets alive for it in scalar registers the loop has none to spare of (they spill into vector registers: six robots +2 VGPRs and 8..12 B of
     //      scratch, two robots with the field 257 VGPRs).
     //      The duals are read where this instantiation keeps them (LDS, or the instance's workspace: the barrier above has drained its stores).
@@ -1727,11 +1669,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         int Ne = P.N, Ke = P.K;
         asm volatile("" : "+s"(Ne), "+s"(Ke));
         const int N1e = Ne + 1, MKe = M_ * Ke;
-        const double *Xe = sm, *Ue = Xe + N1e * NX, *LAMe = Ue + Ne * NU, *SNe = LAMe + N1e * NX, *CSe = SNe + Ne * M_;
-        const double *RVe = CSe + Ne * M_ + N1e * NX + Ne * NU, *XSe = RVe + ((N1e * NX > RG0) ? N1e * NX : RG0);
-        double *gde = DLL ? const_cast<double *>(XSe) + NX + 8 : ws + inst * P.stride2 + P.oDUAL;
-        const int eZPp = N1e * NP, eZO = eZPp + N1e * NP + N1e * MKe, eZUL = eZO + N1e * MKe, eZUU = eZUL + Ne * NU, eZXL = eZUU + Ne * NU, eZXU = eZXL + N1e * NXB;
-        const UArr zp{gde, eZPp}, zo{gde, eZO}, zul{gde, eZUL}, zuu{gde, eZUU}, zxl{gde, eZXL}, zxu{gde, eZXU};
+        const ColLayout<M_, THB> Le(Ne, Ke);
+        const double *Xe = sm + Le.X, *Ue = sm + Le.U, *LAMe = sm + Le.LAM, *SNe = sm + Le.SN, *CSe = sm + Le.CS, *XSe = sm + Le.XS;
+        double *gde = DLL ? sm + Le.end : ws + inst * P.stride2 + P.oDUAL;
+        const UArr zp{gde, Le.ZPp}, zo{gde, Le.ZO}, zul{gde, Le.ZUL}, zuu{gde, Le.ZUU}, zxl{gde, Le.ZXL}, zxu{gde, Le.ZXU};
         double *lg = P.lam_g ? P.lam_g + inst * (size_t)P.ng : nullptr;
         double *lp = P.lam_p ? P.lam_p + inst * (size_t)(2 * NX) : nullptr;
         // initial block X_0 - x0: from stationarity in X_0 (the stage-0 pair / obstacle rows carry 0); lam_p = (the same, 2 Q sum_k (X_k - xs))
@@ -1780,15 +1721,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 // LDS bytes of one instance of the column-per-lane kernel
 template <int M_, int THB> static size_t col_lds_bytes(const KParams &P, bool duals, int fl = 0)      // fl: 2 = + stage factors, 3 = + stage packs (see the kernel)
 {
-    using G = G2<M_, THB>;
-    const size_t N = P.N, N1 = P.N + 1, MK = (size_t)M_ * P.K;
-    size_t d = N1 * G::NX * 3 + N * G::NU * 2 + N * M_ * 2;
-    const size_t rg0 = G::KTS > G::PACK ? G::KTS : G::PACK;
-    d += (N1 * G::NX > rg0) ? N1 * G::NX : rg0;
-    d += G::NX + 8;
-    if (duals) d += 2 * N1 * G::NP + 2 * N1 * MK + 4 * N * G::NU + 2 * N1 * G::NXB;
-    if (duals && fl >= 2) d += N * G::KTS;
-    if (duals && fl >= 3) d += N1 * GC<M_, THB>::PACK;
+    const ColLayout<M_, THB> L(P.N, P.K);
+    size_t d = L.end;
+    if (duals) d += L.dual;
+    if (duals && fl >= 2) d += (size_t)P.N * G2<M_, THB>::KTS;
+    if (duals && fl >= 3) d += (size_t)(P.N + 1) * GC<M_, THB>::PACK;
     return d * sizeof(double);
 }
 // slacks / duals in LDS: up to four robots, when eight instances still share a CU
@@ -1916,6 +1853,12 @@ size_t col_kernel_bytes(const KParams &P, int m, int shape)
 {
     SolveVariant v;
     return select_solve_col(P, m, shape, false, &v) ? v.lds : 0;
+}
+
+// doubles of the slack / dual block of one instance (ColLayout): what the workspace carve-up reserves at KParams::oDUAL (0 if m is not supported)
+int64_t col_dual_doubles(const KParams &P, int m)
+{
+    return for_team_size(m, (int64_t)0, [&](auto M) { return (int64_t)(P.thb ? ColLayout<decltype(M)::value, 1>(P.N, P.K).dual : ColLayout<decltype(M)::value, 0>(P.N, P.K).dual); });
 }
 #endif      // entry points
 

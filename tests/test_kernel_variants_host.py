@@ -2,6 +2,7 @@
 the launch-variant descriptor is declared, exported and bound, the library's choice of kernel, shape and instantiation (pure host arithmetic,
 reached through the device-free descriptor with the 256 compute units of an MI355X) is what the table, the pinning tests and the built code
 object say, and the recipes' inputs are ones on which the oracle agrees with itself."""
+import json
 import os
 import re
 import subprocess
@@ -79,10 +80,15 @@ CUS = 256      # compute units of an MI355X
 
 
 def test_every_row_is_named_by_its_recipe(built):
-    """the device-free descriptor names each row of the table for the row's own recipe (pin, B, ordered, field)"""
+    """the device-free descriptor names each row of the table for the row's own recipe (pin, B, ordered, field), with exactly the LDS bytes
+    recorded for the row in tests/golden/col_lds_bytes.json (the same call on the build before the LDS layout had one definition)"""
+    with open(os.path.join(ROOT, "tests", "golden", "col_lds_bytes.json")) as f:
+        lds_bytes = json.load(f)
+    assert sorted(lds_bytes) == sorted(KV.row_id(r) for r in KV.TABLE)
     for r in KV.TABLE:
         rc, got, lds, code = KV.variant_of_config(KV.c_config(R.NLPConfig(**r.cfg), r.max_iter), r.pin, CUS, r.B, r.ordered, r.obs_field)
         assert rc == 0 and got == r.row and 0 <= lds <= 160 * 1024, (r.row, rc, got, lds)
+        assert lds == lds_bytes[KV.row_id(r)], (r.row, lds, lds_bytes[KV.row_id(r)])
         assert code == (4 if (got[0] == 3 and got[4] > 64) else got[0]), (r.row, code)
 
 
