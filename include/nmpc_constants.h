@@ -1,8 +1,8 @@
 /*
  * nmpc_constants.h — constants of the interior-point algorithm that the HIP kernels (csrc/) and the CPU oracles (oracle/) must
  * agree on: the GPU parity tests assert equal statuses and (almost everywhere) equal iteration counts, so a constant that differed
- * between the two sides would make them diverge silently.  One definition, included by csrc/nmpc_device.h, csrc/nmpc_lidar.hip,
- * oracle/nmpc_oracle.c and oracle/lidar_oracle.c.  Plain C preprocessor constants, no dependencies.
+ * between the two sides would make them diverge silently.  One definition, included by csrc/nmpc_device.h, csrc/nmpc_ipm.h (the
+ * kernels' controller), oracle/nmpc_oracle.c and oracle/lidar_oracle.c.  Plain C preprocessor constants, no dependencies.
  */
 #ifndef NMPC_CONSTANTS_H_
 #define NMPC_CONSTANTS_H_

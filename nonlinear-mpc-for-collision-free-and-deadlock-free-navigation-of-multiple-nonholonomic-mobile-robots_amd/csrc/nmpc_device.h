@@ -1,4 +1,5 @@
-// nmpc_device.h — kernel parameter block shared by nmpc_kernels.hip and nmpc_api.cpp.
+// nmpc_device.h — the kernel parameter block, the launch descriptors and the launcher declarations shared by nmpc_api.cpp and the three swarm
+// solve kernels (nmpc_kernels.hip, nmpc_solve_lds.hip, nmpc_solve_col.hip, the latter two through nmpc_solve_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -15,6 +15,11 @@
 // contiguous so a wave reads it with unit-stride 8-byte lanes.  The stage working set of the
 // Riccati sweep (P, P[A B], Qxx/Qux/Quu, the 3x2 Jacobian entries sin/cos per robot) lives in
 // LDS.  All arithmetic is IEEE fp64.
+//
+// This is kernel 1, the HBM-resident solve: the library's choice where the iterate of the LDS-resident kernels no longer fits a CU's LDS
+// (long horizons), and pin 1.  It shares the parameter block (nmpc_device.h) with nmpc_api.cpp and the other two swarm kernels, the
+// controller of the iteration (nmpc_ipm.h) with every solve kernel, and geometry, pair decoding, wave reductions, bounds, interior push and
+// the result write (nmpc_solve_common.h) with the LDS-resident ones.  Its constraint arithmetic is its own (see slot_h below).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -25,62 +30,21 @@
 namespace nmpc {
 
 // ------------------------------------------------------------------------------------------
-// block-wide reductions (wave64 butterfly, then LDS across waves)
-template <int TPB> __device__ __forceinline__ double blk_sum(double v, double *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if constexpr (TPB > 64) {
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < TPB / 64; w++) t += red[w];
-        v = t;
-    }
-    return v;
-}
-template <int TPB> __device__ __forceinline__ double blk_max(double v, double *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    if constexpr (TPB > 64) {
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double t = red[0];
-#pragma unroll
-        for (int w = 1; w < TPB / 64; w++) t = fmax(t, red[w]);
-        v = t;
-    }
-    return v;
-}
-template <int TPB> __device__ __forceinline__ double blk_min(double v, double *red) { return -blk_max<TPB>(-v, red); }
-
-// ------------------------------------------------------------------------------------------
-template <int M_> struct Geo {
-    static constexpr int NX = 3 * M_, NU = 2 * M_, NP = M_ * (M_ - 1) / 2, NZ = NX + NU;
-};
-
-// index of pair (a,b), a<b, in lexicographic order (C6:288-306)
-template <int M_> __device__ __forceinline__ int pair_index(int a, int b) { return a * (2 * M_ - a - 1) / 2 + (b - a - 1); }
-
+// The inequality slots of one stage in this kernel's workspace order: control bounds, state bounds, pair rows, obstacle rows.  This constraint
+// arithmetic (slot_h, slot_jd, jxT_robot, and the stage-0 pre-check below) is this kernel's own: plain products and sums, which round differently
+// from the fma-pinned h_pair / h_obs of the LDS-resident kernels (nmpc_solve_common.h).  It is not unified with them: that would move this kernel's results.
 __device__ __forceinline__ bool slot_active(const KParams &P, int k, int s)
 {
     if (s < P.o_xl) return k < P.N;
     if (s < P.o_pr) return k >= 1;
     return k >= 1 && k <= P.N - 1;
 }
-__device__ __forceinline__ int bnd_state(const KParams &P, int s) { return P.thb ? s : 3 * (s >> 1) + (s & 1); }
-__device__ __forceinline__ double bnd_val(const KParams &P, int s) { return (P.thb && (s % 3 == 2)) ? P.thmax : P.xymax; }
-__device__ __forceinline__ double lbu(const KParams &P, int c) { return (c & 1) ? -P.wmax : -P.vmax; }
 
 // value of inequality slot s at stage k; x,u point at the stage's state / control block
 template <int M_>
-__device__ __forceinline__ double slot_h(const KParams &P, const int *sPi, const int *sPj, int k, int s, const double *x, const double *u)
+__device__ __forceinline__ double slot_h(const KParams &P, int k, int s, const double *x, const double *u)
 {
-    constexpr int NU = Geo<M_>::NU;
+    constexpr int NU = G2<M_, 0>::NU;
     if (s < P.o_xl) {
         if (k >= P.N) return 1.0;
         return (s < NU) ? (u[s] - lbu(P, s)) : (-lbu(P, s - NU) - u[s - NU]);
@@ -88,12 +52,13 @@ __device__ __forceinline__ double slot_h(const KParams &P, const int *sPi, const
     if (s < P.o_pr) {
         if (k < 1) return 1.0;
         int sl = (s < P.o_xu) ? s - P.o_xl : s - P.o_xu;
-        double v = x[bnd_state(P, sl)], b = bnd_val(P, sl);
+        double v = x[bst(P.thb, sl)], b = bvl(P, P.thb, sl);
         return (s < P.o_xu) ? (v + b) : (b - v);
     }
     if (k < 1 || k > P.N - 1) return 1.0;
     if (s < P.o_ob) {
-        int pq = s - P.o_pr, i = sPi[pq], j = sPj[pq];
+        int pq = s - P.o_pr, i, j;
+        pair_of<M_>(pq, i, j);
         double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1];
         return dx * dx + dy * dy - P.dmin2;
     }
@@ -104,18 +69,19 @@ __device__ __forceinline__ double slot_h(const KParams &P, const int *sPi, const
 
 // (Jx_k d)[s] for x-slots, (Ju_k du)[s] for u-slots
 template <int M_>
-__device__ __forceinline__ double slot_jd(const KParams &P, const int *sPi, const int *sPj, int k, int s, const double *x, const double *dx_,
+__device__ __forceinline__ double slot_jd(const KParams &P, int k, int s, const double *x, const double *dx_,
                                           const double *du)
 {
-    constexpr int NU = Geo<M_>::NU;
+    constexpr int NU = G2<M_, 0>::NU;
     if (s < P.o_xl) return (s < NU) ? du[s] : -du[s - NU];
     if (s < P.o_pr) {
         int sl = (s < P.o_xu) ? s - P.o_xl : s - P.o_xu;
-        double v = dx_[bnd_state(P, sl)];
+        double v = dx_[bst(P.thb, sl)];
         return (s < P.o_xu) ? v : -v;
     }
     if (s < P.o_ob) {
-        int pq = s - P.o_pr, i = sPi[pq], j = sPj[pq];
+        int pq = s - P.o_pr, i, j;
+        pair_of<M_>(pq, i, j);
         double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1];
         return 2 * dx * (dx_[3 * i] - dx_[3 * j]) + 2 * dy * (dx_[3 * i + 1] - dx_[3 * j + 1]);
     }
@@ -144,7 +110,7 @@ __device__ __forceinline__ void jxT_robot(const KParams &P, int k, int i, const 
 #pragma unroll
     for (int j = 0; j < (P.pairs ? M_ : 0); j++) {
         if (j == i) continue;
-        int pq = (i < j) ? pair_index<M_>(i, j) : pair_index<M_>(j, i);
+        int pq = (i < j) ? pidx<M_>(i, j) : pidx<M_>(j, i);
         double z = v(P.o_pr + pq);
         o0 += 2 * (xi - x[3 * j]) * z;
         o1 += 2 * (yi - x[3 * j + 1]) * z;
@@ -164,7 +130,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                                                      int32_t *__restrict__ status_out, int32_t *__restrict__ iters_out,
                                                      double *__restrict__ kkt_out, double *__restrict__ ws)
 {
-    constexpr int NX = Geo<M_>::NX, NU = Geo<M_>::NU, NP = Geo<M_>::NP, NZ = Geo<M_>::NZ;
+    constexpr int NX = G2<M_, 0>::NX, NU = G2<M_, 0>::NU, NP = G2<M_, 0>::NP, NZ = G2<M_, 0>::NZ;
     const int tid = threadIdx.x;
     const int N = P.N, NH = P.nh;
     const double T = P.T;
@@ -179,7 +145,6 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
     __shared__ double sX[NX], sU[NU], sCk[NX], sA[M_], sB[M_], sSn[M_], sCs[M_];
     __shared__ double sE[3 * (NP > 0 ? NP : 1)];
     __shared__ double sXs[NX], sRed[TPB / 64 + 1];
-    __shared__ int sPi[NP > 0 ? NP : 1], sPj[NP > 0 ? NP : 1];
     __shared__ int sFail;
 
     // ---- workspace carve-up (doubles)
@@ -199,40 +164,24 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
     const double *wi = w0 + inst * (size_t)P.nvar;
     double *wo = w_out + inst * (size_t)P.nvar;
 
-    // pair tables
-    if (tid == 0) {
-        int q = 0;
-        for (int i = 0; i < M_; i++) for (int j = i + 1; j < M_; j++) { sPi[q] = i; sPj[q] = j; q++; }
-        sFail = 0;
-    }
+    if (tid == 0) sFail = 0;
     for (int c = tid; c < NX; c += TPB) sXs[c] = pp[NX + c];
     // ---- load the start: X_0 := x0 (C6:278 pins it), push into the interior of the simple bounds
-    const double bp = 1e-2;
+    constexpr double bp = NMPC_BOUND_PUSH;
     for (int e = tid; e < (N + 1) * NX; e += TPB) {
         int k = e / NX, c = e - k * NX;
-        double v = (k == 0) ? pp[c] : wi[e];
-        if (k >= 1) {
-            int d = c % 3;
-            if (d < 2 || P.thb) {
-                double b = (d == 2) ? P.thmax : P.xymax, px = fmin(bp * fmax(1.0, b), bp * 2.0 * b);
-                v = fmin(fmax(v, -b + px), b - px);
-            }
-        }
-        X[e] = v;
+        X[e] = (k == 0) ? pp[c] : push_state(P, P.thb, c, wi[e]);
         LAM[e] = 0.0;
     }
-    for (int e = tid; e < N * NU; e += TPB) {
-        int c = e % NU;
-        double lo = lbu(P, c), hi = -lo, pu = fmin(bp * fmax(1.0, fabs(lo)), bp * (hi - lo));
-        U[e] = fmin(fmax(wi[(size_t)(N + 1) * NX + e], lo + pu), hi - pu);
-    }
+    for (int e = tid; e < N * NU; e += TPB) U[e] = push_control(P, e % NU, wi[(size_t)(N + 1) * NX + e]);
     __syncthreads();
 
     // ---- stage-0 pair / obstacle rows act on the pinned state: feasibility pre-check
     {
         double bad = 0.0;
         for (int q = tid; q < NPA; q += TPB) {
-            int i = sPi[q], j = sPj[q];
+            int i, j;
+            pair_of<M_>(q, i, j);
             double dx = pp[3 * i] - pp[3 * j], dy = pp[3 * i + 1] - pp[3 * j + 1];
             if (dx * dx + dy * dy < P.dmin2 - NMPC_X0_TOL) bad = 1.0;
         }
@@ -241,16 +190,11 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
             double dx = pp[3 * i] - P.obs[3 * o], dy = pp[3 * i + 1] - P.obs[3 * o + 1];
             if (sqrt(dx * dx + dy * dy) - P.robdim - P.obs[3 * o + 2] < P.margin - NMPC_X0_TOL) bad = 1.0;
         }
-        bad = blk_max<TPB>(bad, sRed);
+        bad = wmax<TPB>(bad, sRed);
         if (bad > 0.0) {
             for (int e = tid; e < (N + 1) * NX; e += TPB) wo[e] = X[e];
             for (int e = tid; e < N * NU; e += TPB) wo[(size_t)(N + 1) * NX + e] = U[e];
-            if (tid == 0) {
-                if (obj_out) obj_out[inst] = NAN;
-                if (status_out) status_out[inst] = NMPC_STATUS_INFEASIBLE_X0;
-                if (iters_out) iters_out[inst] = 0;
-                if (kkt_out) kkt_out[inst] = INFINITY;
-            }
+            if (tid == 0) write_result(inst, NAN, NMPC_STATUS_INFEASIBLE_X0, 0, INFINITY, obj_out, status_out, iters_out, kkt_out);
             return;
         }
     }
@@ -271,8 +215,8 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
             fs += P.q[0] * e0 * e0 + P.q[1] * e1 * e1 + P.q[2] * e2 * e2 + P.r[0] * u[0] * u[0] + P.r[1] * u[1] * u[1];
         }
         for (int k = 0; k <= N; k++)
-            for (int s = tid; s < NH; s += TPB) H[k * NH + s] = slot_h<M_>(P, sPi, sPj, k, s, X + k * NX, U + (k < N ? k : 0) * NU);
-        return blk_sum<TPB>(fs, sRed);
+            for (int s = tid; s < NH; s += TPB) H[k * NH + s] = slot_h<M_>(P, k, s, X + k * NX, U + (k < N ? k : 0) * NU);
+        return wsum<TPB>(fs, sRed);
     };
     // merit pieces at the trial point (X + a dX, U + a dU, S + a dS); nothing is stored
     auto eval_trial = [&](double a, double mu, double &phi, double &theta) {
@@ -298,16 +242,16 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
             for (int s = tid; s < NH; s += TPB)
                 if (slot_active(P, k, s)) {
                     double st = S[k * NH + s] + a * DS[k * NH + s];
-                    double h = slot_h<M_>(P, sPi, sPj, k, s, sX, sU);
+                    double h = slot_h<M_>(P, k, s, sX, sU);
                     lg += log(st);
                     if (ELSLOT(s)) { const double tt = EL[k * NH + s] + a * DEL[k * NH + s]; lg += log(tt); fs += rho * tt; th += fabs(h + tt - st); }
                     else
                     th += fabs(h - st);
                 }
         }
-        fs = blk_sum<TPB>(fs, sRed);
-        lg = blk_sum<TPB>(lg, sRed);
-        theta = blk_sum<TPB>(th, sRed);
+        fs = wsum<TPB>(fs, sRed);
+        lg = wsum<TPB>(lg, sRed);
+        theta = wsum<TPB>(th, sRed);
         phi = fs - mu * lg;
     };
 
@@ -331,34 +275,25 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
 
     double delta_last = 0.0, nu_pen = 1.0, kkt = INFINITY;
     bool need_shift = false;
-    int n_tiny = 0, n_restart = 0;      // consecutive iterations with a step length below 1e-10 (stall -> restart, then NMPC_STATUS_STALLED)
-    double mh0 = 0.0, mh1 = 0.0, mh2 = 0.0, mh_mu = -1.0, mh_nu = -1.0;
-    int mcount = 0;
+    ipm::Ladder lad;      // stall / restart ladder: tiny steps -> barrier restarts -> cold retries -> NMPC_STATUS_STALLED (nmpc_ipm.h)
+    ipm::MeritRef mref_h;
     int iter = 0, status = NMPC_STATUS_MAX_ITER;
     const double n_ineq = (double)P.n_ineq;
     // (Re)start of the barrier iteration from the current primal point, or — cold — from the reference's cold start X_k = x0, U = 0
     // (C6:398-400; the cold-start retry of NMPC_COLD_RETRY_ITERS): interior push, slacks onto the constraint values, duals mu/s, multipliers 0
-    int n_cold = 0, it_base = 0;
     auto do_restart = [&](bool cold) {
-        if (cold) { n_cold++; it_base = iter; el = n_cold >= 2; mu = P.mu_init; n_tiny = 0; n_restart = 0; }      // the second restart of last resort is the elastic phase
+        if (cold) { ipm::cold_retry_begin(lad, iter); el = lad.n_cold >= 2; mu = P.mu_init; }      // the second restart of last resort is the elastic phase
         for (int e = tid + NX; e < (N + 1) * NX; e += TPB) {
             if (cold) X[e] = X[e % NX];
-            const int d = (e % NX) % 3;
-            if (d < 2 || P.thb) {
-                double b = (d == 2) ? P.thmax : P.xymax, px = fmin(bp * fmax(1.0, b), bp * 2.0 * b);
-                X[e] = fmin(fmax(X[e], -b + px), b - px);
-            }
+            X[e] = push_state(P, P.thb, e % NX, X[e]);
             LAM[e] = 0.0;
         }
-        for (int e = tid; e < N * NU; e += TPB) {
-            double lo = lbu(P, e % NU), hi = -lo, pu = fmin(bp * fmax(1.0, fabs(lo)), bp * (hi - lo));
-            U[e] = fmin(fmax(cold ? 0.0 : U[e], lo + pu), hi - pu);
-        }
+        for (int e = tid; e < N * NU; e += TPB) U[e] = push_control(P, e % NU, cold ? 0.0 : U[e]);
         __syncthreads();
         f = eval_point();
         __syncthreads();
         init_barrier();
-        delta_last = 0.0; nu_pen = 1.0; need_shift = false; mcount = 0;
+        delta_last = 0.0; nu_pen = 1.0; need_shift = false; mref_h.reset();
     };
 
     for (;;) {
@@ -401,35 +336,27 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                 szmax = fmax(szmax, sv * zv); szmin = fmin(szmin, sv * zv);
             }
         }
-        e_d = blk_max<TPB>(e_d, sRed); e_c = blk_max<TPB>(e_c, sRed); e_h = blk_max<TPB>(e_h, sRed);
-        lsum = blk_sum<TPB>(lsum, sRed); zsum = blk_sum<TPB>(zsum, sRed);
-        szmax = blk_max<TPB>(szmax, sRed); szmin = blk_min<TPB>(szmin, sRed);
-        const double smax = 100.0;
-        double s_d = fmax(smax, (lsum + zsum) / ((double)(N * NX) + n_ineq)) / smax;
-        double s_c = fmax(smax, zsum / fmax(n_ineq, 1.0)) / smax;
-        double E0 = fmax(fmax(e_d / s_d, e_c), fmax(e_h, szmax / s_c));
+        e_d = wmax<TPB>(e_d, sRed); e_c = wmax<TPB>(e_c, sRed); e_h = wmax<TPB>(e_h, sRed);
+        lsum = wsum<TPB>(lsum, sRed); zsum = wsum<TPB>(zsum, sRed);
+        szmax = wmax<TPB>(szmax, sRed); szmin = wmin<TPB>(szmin, sRed);
+        const ipm::OptErr oe = ipm::opt_error(e_d, e_c, e_h, lsum, zsum, szmax, (double)(N * NX) + n_ineq, fmax(n_ineq, 1.0));
+        const double E0 = oe.E0;
         kkt = E0;
-        if (!(E0 == E0)) { if (n_cold < NMPC_COLD_RETRIES && iter < P.max_iter) { do_restart(true); continue; } status = NMPC_STATUS_NUMERIC; break; }
+        if (!(E0 == E0)) { if (ipm::cold_retry_left(lad) && iter < P.max_iter) { do_restart(true); continue; } status = NMPC_STATUS_NUMERIC; break; }
         if (E0 <= P.tol) {
             status = NMPC_STATUS_CONVERGED;
             if (el) {       // the penalty problem's solution solves the NLP only if every elastic variable has closed
                 double tmax = 0.0;
                 for (int e = tid; e < (N + 1) * NH; e += TPB) { int k = e / NH, s = e - k * NH; if (s >= P.o_pr && slot_active(P, k, s)) tmax = fmax(tmax, EL[e]); }
-                if (blk_max<TPB>(tmax, sRed) > NMPC_X0_TOL) status = NMPC_STATUS_STALLED;
+                if (wmax<TPB>(tmax, sRed) > NMPC_X0_TOL) status = NMPC_STATUS_STALLED;
             }
             break;
         }
         if (iter >= P.max_iter) { status = NMPC_STATUS_MAX_ITER; break; }
-        if (n_cold < NMPC_COLD_RETRIES && iter - it_base >= NMPC_COLD_RETRY_ITERS) { do_restart(true); continue; }
+        if (ipm::cold_retry_due(lad, iter)) { do_restart(true); continue; }
         // ================= monotone barrier update (IPOPT eq. 7)
-        const double mu_min = P.tol / 10.0;
-        for (;;) {
-            double cm = fmax(fabs(szmax - mu), fabs(szmin - mu));
-            double Emu = fmax(fmax(e_d / s_d, e_c), fmax(e_h, cm / s_c));
-            if (mu > mu_min && Emu <= 10.0 * mu) mu = fmax(mu_min, fmin(0.2 * mu, pow(mu, 1.5)));
-            else break;
-        }
-        const double tau = fmax(0.99, 1.0 - mu);
+        mu = ipm::barrier_update(mu, P.tol, e_d / oe.s_d, e_c, e_h, szmax, szmin, oe.s_c);
+        const double tau = ipm::frac_to_boundary(mu);
 
         // ================= per-stage gradient pieces (all stages in parallel)
         for (int it = tid; it < (N + 1) * M_; it += TPB) {
@@ -471,7 +398,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
 
         // ================= Riccati sweep with inertia correction (IPOPT alg. IC)
         // first trial: delta = 0, except right after an iteration that needed a shift (then a quarter of that shift directly)
-        double delta = need_shift ? fmax(1e-20, 0.25 * delta_last) : 0.0;
+        double delta = ipm::shift_first(need_shift, delta_last);
         // Partial re-factorisation (include/nmpc_constants.h): [P | p] entering every NMPC_CKPT_EVERY-th stage is saved; a rejected pivot at
         // stage kf escalates the shift and resumes at the saved stage NMPC_RESUME_STAGE(kf, N), the stages above keep their gains.
         int ntry = 0;
@@ -487,7 +414,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                 for (int c = tid; c < NX; c += TPB) sPv[c] = GX[N * NX + c];
                 __syncthreads();
                 for (int s = tid; s < P.nxb; s += TPB) {
-                    int c = bnd_state(P, s);
+                    int c = bst(P.thb, s);
                     sP[c * NX + c] += Z[N * NH + P.o_xl + s] / S[N * NH + P.o_xl + s] + Z[N * NH + P.o_xu + s] / S[N * NH + P.o_xu + s];
                 }
             } else {
@@ -533,7 +460,8 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                 // pair blocks E_ij = 4 sigma dp dp^T - 2 z I of this stage's Hessian (k>=1)
                 if (k >= 1) {
                     for (int q = tid; q < NP; q += TPB) {
-                        int i = sPi[q], j = sPj[q];
+                        int i, j;
+                        pair_of<M_>(q, i, j);
                         double dx = sX[3 * i] - sX[3 * j], dy = sX[3 * i + 1] - sX[3 * j + 1];
                         double zz = P.pairs ? Z[k * NH + P.o_pr + q] : 0.0, sg = P.pairs ? zz / S[k * NH + P.o_pr + q] : 0.0;
                         if (el && P.pairs) sg = 1.0 / (S[k * NH + P.o_pr + q] / zz + EL[k * NH + P.o_pr + q] / (rho - zz));
@@ -579,13 +507,14 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                     }
                     __syncthreads();
                     for (int s = tid; s < P.nxb; s += TPB) {
-                        int c = bnd_state(P, s);
+                        int c = bst(P.thb, s);
                         sP[c * NX + c] += Z[k * NH + P.o_xl + s] / S[k * NH + P.o_xl + s] + Z[k * NH + P.o_xu + s] / S[k * NH + P.o_xu + s];
                     }
                     __syncthreads();
                     // off-diagonal 2x2 blocks: -E_ij ; diagonal blocks: sum_j E_ij (ascending partner) + obstacle terms
                     for (int e = tid; e < NP * 4; e += TPB) {
-                        int q = e >> 2, w = e & 3, i = sPi[q], j = sPj[q];
+                        int q = e >> 2, w = e & 3, i, j;
+                        pair_of<M_>(q, i, j);
                         int rr = w >> 1, cc = w & 1;
                         double ev = sE[3 * q + rr + cc];
                         sP[(3 * i + rr) * NX + 3 * j + cc] -= ev;
@@ -596,7 +525,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
 #pragma unroll
                         for (int j = 0; j < M_; j++) {
                             if (j == i) continue;
-                            int q = (i < j) ? pair_index<M_>(i, j) : pair_index<M_>(j, i);
+                            int q = (i < j) ? pidx<M_>(i, j) : pidx<M_>(j, i);
                             e00 += sE[3 * q]; e01 += sE[3 * q + 1]; e11 += sE[3 * q + 2];
                         }
                         for (int o = 0; o < P.K; o++) {
@@ -680,14 +609,12 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
             if (tid == 0) sFail = 0;
             __syncthreads();
             ntry++;
-            if (delta == 0.0) delta = (delta_last == 0.0) ? 1e-4 : fmax(1e-20, delta_last / 3.0);
-            else delta *= (delta_last == 0.0) ? 100.0 : NMPC_SHIFT_ESCALATION;
-            if (delta > 1e20) break;
+            delta = ipm::shift_next(delta, delta_last);
+            if (ipm::shift_exhausted(delta)) break;
             kst = NMPC_RESUME_STAGE(kf, N);
         }
-        if (!ok) { if (n_cold < NMPC_COLD_RETRIES) { do_restart(true); iter++; continue; } status = NMPC_STATUS_NUMERIC; break; }
-        if (delta > 0.0) delta_last = delta;
-        need_shift = delta > 0.0 && (ntry > 0 || delta > 1e-6);
+        if (!ok) { if (ipm::cold_retry_left(lad)) { do_restart(true); iter++; continue; } status = NMPC_STATUS_NUMERIC; break; }
+        ipm::shift_accept(delta, ntry, delta_last, need_shift);
 
         // ================= forward sweep (serial over stages; dx_k lives in LDS)
         for (int c = tid; c < NX; c += TPB) { sX[c] = 0.0; DX[c] = 0.0; }
@@ -728,14 +655,14 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                 double ds, dz;
                 if (ELSLOT(s)) {
                     const double tv = EL[e], rz = rho - zv, D_ = sv / zv + tv / rz, q_ = H[e] - mu / zv + mu / rz;
-                    dz = -(slot_jd<M_>(P, sPi, sPj, k, s, x, dxk, duk) + q_) / D_;
+                    dz = -(slot_jd<M_>(P, k, s, x, dxk, duk) + q_) / D_;
                     ds = (mu - sv * zv - sv * dz) / zv;
                     const double dt = (mu - tv * rz + tv * dz) / rz;
                     DEL[e] = dt;
                     if (dt < 0.0) a_p = fmin(a_p, -tau * tv / dt);
                     if (dz > 0.0) a_d = fmin(a_d, tau * rz / dz);
                 } else {
-                ds = slot_jd<M_>(P, sPi, sPj, k, s, x, dxk, duk) + (H[e] - sv);
+                ds = slot_jd<M_>(P, k, s, x, dxk, duk) + (H[e] - sv);
                 dz = (mu - sv * zv - zv * ds) / sv;
                 }
                 DS[e] = ds; DZ[e] = dz;
@@ -744,8 +671,8 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                 if (dz < 0.0) a_d = fmin(a_d, -tau * zv / dz);
             }
         }
-        a_p = blk_min<TPB>(a_p, sRed);
-        a_d = blk_min<TPB>(a_d, sRed);
+        a_p = wmin<TPB>(a_p, sRed);
+        a_d = wmin<TPB>(a_d, sRed);
         __syncthreads();
 
         // ================= multipliers of the QP: adjoint recursion, serial over stages
@@ -766,7 +693,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
 #pragma unroll
                     for (int j = 0; j < (P.pairs ? M_ : 0); j++) {
                         if (j == i) continue;
-                        int q = (i < j) ? pair_index<M_>(i, j) : pair_index<M_>(j, i);
+                        int q = (i < j) ? pidx<M_>(i, j) : pidx<M_>(j, i);
                         double zz = zk[P.o_pr + q];
                         w0_ -= 2 * zz * (dx[3 * i] - dx[3 * j]);
                         w1_ -= 2 * zz * (dx[3 * i + 1] - dx[3 * j + 1]);
@@ -807,32 +734,21 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
             int k = e / NH, s = e - k * NH;
             if (slot_active(P, k, s)) { dphi -= mu * DS[e] / S[e]; if (ELSLOT(s)) dphi += (rho - mu / EL[e]) * DEL[e]; }
         }
-        dphi = blk_sum<TPB>(dphi, sRed);
+        dphi = wsum<TPB>(dphi, sRed);
         for (int e = NX + tid; e < (N + 1) * NX; e += TPB) mult_max = fmax(mult_max, fabs(LAMN[e]));
-        mult_max = blk_max<TPB>(mult_max, sRed);
-        if (th0 > 0.0) {
-            // Nocedal-Wright (18.36), rho = 0.1; capped by the multiplier norm it cannot exceed in exact arithmetic
-            double nut = fmin(dphi / ((1.0 - 0.1) * th0), mult_max / (1.0 - 0.1));
-            nu_pen = fmax(1.0, 0.5 * nu_pen);
-            if (nu_pen < nut) nu_pen = nut + 1.0;
-        }
+        mult_max = wmax<TPB>(mult_max, sRed);
+        if (th0 > 0.0) nu_pen = ipm::penalty_update(nu_pen, dphi, th0, mult_max);
         const double D = dphi - nu_pen * th0;
         double alpha = a_p;
-        if (mh_mu != mu || mh_nu != nu_pen) { mcount = 0; mh_mu = mu; mh_nu = nu_pen; }
-        const double m0 = phi0 + nu_pen * th0;
-        double mref = m0;
-        if (mcount > 0) mref = fmax(mref, mh0);
-        if (mcount > 1) mref = fmax(mref, mh1);
-        if (mcount > 2) mref = fmax(mref, mh2);
-        mh2 = mh1; mh1 = mh0; mh0 = m0; if (mcount < 3) mcount++;
+        const double mref = mref_h.reference(mu, nu_pen, phi0 + nu_pen * th0);
         for (int ls = 0; ls < 30; ls++) {
             double phit, tht;
             eval_trial(alpha, mu, phit, tht);
-            if (phit + nu_pen * tht <= mref + 1e-4 * alpha * D + 1e-13 * fabs(phi0)) break;
+            if (ipm::armijo(phit + nu_pen * tht, mref, alpha, D, phi0)) break;
             if (ls < 29) alpha *= 0.5;
         }
         a_d = fmin(a_d, alpha);      // the duals never step further than the primal variables actually moved
-        n_tiny = (alpha < 1e-10) ? n_tiny + 1 : 0;
+        ipm::count_step(lad, alpha);
         __syncthreads();
         // ================= accept: primal / slack step alpha, dual step a_d with safeguard (IPOPT eq. 16)
         for (int e = tid; e < (N + 1) * NX; e += TPB) {
@@ -855,11 +771,11 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
         f = eval_point();
         __syncthreads();
         iter++;
-        if (n_tiny >= 5) {
-            if (n_restart >= 3) { if (n_cold < NMPC_COLD_RETRIES) { do_restart(true); continue; } status = NMPC_STATUS_STALLED; break; }
+        if (ipm::stalled(lad)) {
+            if (ipm::restarts_used_up(lad)) { if (ipm::cold_retry_left(lad)) { do_restart(true); continue; } status = NMPC_STATUS_STALLED; break; }
             // barrier restart from the current primal point (restoration in miniature, see the oracle)
-            n_restart++; n_tiny = 0;
-            mu = fmax(mu, P.mu_init);
+            ipm::barrier_restart_begin(lad);
+            mu = ipm::restart_mu(mu, P.mu_init);
             do_restart(false);
         }
     }
@@ -868,12 +784,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
     __syncthreads();
     for (int e = tid; e < (N + 1) * NX; e += TPB) wo[e] = X[e];
     for (int e = tid; e < N * NU; e += TPB) wo[(size_t)(N + 1) * NX + e] = U[e];
-    if (tid == 0) {
-        if (obj_out) obj_out[inst] = f;
-        if (status_out) status_out[inst] = status;
-        if (iters_out) iters_out[inst] = iter;
-        if (kkt_out) kkt_out[inst] = kkt;
-    }
+    if (tid == 0) write_result(inst, f, status, iter, kkt, obj_out, status_out, iters_out, kkt_out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -886,7 +797,7 @@ __global__ __launch_bounds__(256) void eval_kernel(const KParams P, const PoseRe
                                                     double *__restrict__ f_out, double *__restrict__ g_out)
 {
     constexpr int M_ = MS % NMPC_EVAL_OBS, OS = MS / NMPC_EVAL_OBS;
-    constexpr int NX = Geo<M_>::NX, NU = Geo<M_>::NU, NP = Geo<M_>::NP;
+    constexpr int NX = G2<M_, 0>::NX, NU = G2<M_, 0>::NU, NP = G2<M_, 0>::NP;
     const int N = P.N;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)B * (N + 1);
@@ -947,7 +858,7 @@ __global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, cons
                                                             double *__restrict__ res_out, double *__restrict__ grad_out)
 {
     constexpr int M_ = MS % NMPC_EVAL_OBS, OS = MS / NMPC_EVAL_OBS;
-    constexpr int NX = Geo<M_>::NX, NU = Geo<M_>::NU, NP = Geo<M_>::NP;
+    constexpr int NX = G2<M_, 0>::NX, NU = G2<M_, 0>::NU, NP = G2<M_, 0>::NP;
     const int N = P.N;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)B * (N + 1);
@@ -995,7 +906,7 @@ __global__ __launch_bounds__(256) void kkt_residual_kernel(const KParams P, cons
             kkt_max(eq, fabs(xn[3 * i] - (xi + P.T * v * c))); kkt_max(eq, fabs(xn[3 * i + 1] - (yi + P.T * v * s))); kkt_max(eq, fabs(xn[3 * i + 2] - (th + P.T * om)));
             for (int j = 0; j < (P.pairs ? M_ : 0); j++) {
                 if (j == i) continue;
-                const int q = i < j ? pair_index<M_>(i, j) : pair_index<M_>(j, i);
+                const int q = i < j ? pidx<M_>(i, j) : pidx<M_>(j, i);
                 const double dx = xi - x[3 * j], dy = yi - x[3 * j + 1], l = lk[NX + q];
                 g0 += 2.0 * dx * l; g1 += 2.0 * dy * l;
                 if (i < j) row(l, dx * dx + dy * dy, P.dmin2);
@@ -1026,7 +937,7 @@ __global__ __launch_bounds__(256) void shift_kernel(const KParams P, int B, cons
 {
     // keep_status (nmpc_step_batch): an instance whose solve ended with a numerical failure (2) or an infeasible x0 (3) — possibly a non-finite
     // iterate — keeps its guess and its x0: nothing of it is overwritten, the caller can still apply a fallback
-    constexpr int NX = Geo<M_>::NX, NU = Geo<M_>::NU;
+    constexpr int NX = G2<M_, 0>::NX, NU = G2<M_, 0>::NU;
     const int N = P.N;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)B * P.nvar;
@@ -1096,7 +1007,7 @@ template <int M_> static hipError_t launch_kkt_m(const KParams &P, const PoseRef
 template <int M_> static hipError_t launch_shift_m(const KParams &P, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st)
 {
     long total = (long)B * P.nvar;
-    hipLaunchKernelGGL((shift_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w_in, w_next, x0n, x0_stride ? x0_stride : Geo<M_>::NX, keep_status);
+    hipLaunchKernelGGL((shift_kernel<M_>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, p, w_in, w_next, x0n, x0_stride ? x0_stride : G2<M_, 0>::NX, keep_status);
     return hipGetLastError();
 }
 

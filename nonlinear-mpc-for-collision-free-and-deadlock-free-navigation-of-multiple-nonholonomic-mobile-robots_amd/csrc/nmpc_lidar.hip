@@ -23,11 +23,12 @@
 #include <string.h>
 
 #include <type_traits>
-#include "../../include/nmpc_constants.h"      // cold-start retry and inertia constants shared with the main solver and the oracles
+#include "nmpc_ipm.h"      // the controller of the interior-point iteration, shared with the swarm kernels (and through it include/nmpc_constants.h)
 #include "../../include/nmpc_lidar.h"
 #include "../../include/nmpc_debug.h"
 
 namespace nmpc_lidar {
+namespace ipm = nmpc::ipm;
 
 struct LParams {
     int32_t N, Nc, R, ns, max_iter, nvar, ng, np, n_ineq;      // n_ineq: finite bounds of the free variables (stages 1..N and the controls)
@@ -285,19 +286,19 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
     };
 
     double mu = P.mu_init, f = 0.0, th0 = 0.0, e_c = 0.0;
-    int it = 0, n_tiny = 0, n_restart = 0, status = NMPC_STATUS_MAX_ITER;
+    int it = 0, status = NMPC_STATUS_MAX_ITER;
 #ifdef NMPC_LIDAR_PROFILE
     long long prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = clock64();
 #endif
     // cold-start retry (the restoration of last resort of the main solver, same constants; see oracle/lidar_oracle.c)
-    int n_cold = 0, it_base = 0;
+    ipm::Ladder lad;
     bool cold = false;
     bool need_shift = false, restarting = false;
     double delta_last = 0.0, nu_pen = 1.0, kkt = INFINITY;
-    double mh0 = 0, mh1 = 0, mh2 = 0, mh_mu = -1, mh_nu = -1;
-    int mcount = 0, n_short = 0;      // n_short: successive steps the backtracking shortened (watchdog, include/nmpc_constants.h)
+    ipm::MeritRef mref_h;
+    int n_short = 0;      // successive steps the backtracking shortened (watchdog, include/nmpc_constants.h)
 
-    auto cold_retry = [&]() { cold = true; n_cold++; it_base = it; restarting = true; mu = (n_cold == 1) ? P.mu_init : 10.0 * P.mu_init; n_tiny = 0; n_restart = 0; };
+    auto cold_retry = [&]() { ipm::cold_retry_begin(lad, it); cold = true; restarting = true; mu = (lad.n_cold == 1) ? P.mu_init : 10.0 * P.mu_init; };      // the second retry starts from a ten times larger barrier parameter
     for (;;) {      // (re)start of the barrier iteration
         if (cold) {       // the reference's cold start (V4:184-196): X_k = x0 (pose and scan), U = 0
             for (int k = 1 + lane; k <= N; k += 64) for (int c = 0; c < ns; c++) SV(oV, k, c) = SV(oV, 0, c);
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
         __syncthreads();
         f = eval_point(oV, oU, th0, e_c);
         __syncthreads();
-        delta_last = 0.0; nu_pen = 1.0; need_shift = false; mcount = 0; restarting = false; n_short = 0;
+        delta_last = 0.0; nu_pen = 1.0; need_shift = false; mref_h.reset(); restarting = false; n_short = 0;
 
         for (;;) {
             LP(0);
@@ -401,26 +402,17 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             pu0 = wsum_(pu0); pu1 = wsum_(pu1);
             if (lane == 0) ctrl_rows(Nc - 1, pu0, pu1);       // the held control: the sum over its stages
             e_d = wmax_(e_d); e_h = wmax_(e_h); zsum = wsum_(zsum); lsum = wsum_(lsum); cmax = wmax_(cmax); cmin = wmin_(cmin);
-            const double smax = 100.0;
-            const double s_d = fmax(smax, (lsum + zsum) / (double)(N * ns + n_ineq)) / smax;
-            const double s_c = fmax(smax, zsum / (double)(n_ineq > 0 ? n_ineq : 1)) / smax;
-            const double E0 = uni(fmax(fmax(e_d / s_d, e_c), fmax(e_h, cmax / s_c)));
+            const ipm::OptErr oe = ipm::opt_error(e_d, e_c, e_h, lsum, zsum, cmax, (double)(N * ns + n_ineq), (double)(n_ineq > 0 ? n_ineq : 1));
+            const double s_d = oe.s_d, s_c = oe.s_c, E0 = uni(oe.E0);
             kkt = E0;
-            if (!(E0 == E0)) { if (n_cold < NMPC_COLD_RETRIES && it < P.max_iter) { cold_retry(); break; } status = NMPC_STATUS_NUMERIC; break; }
+            if (!(E0 == E0)) { if (ipm::cold_retry_left(lad) && it < P.max_iter) { cold_retry(); break; } status = NMPC_STATUS_NUMERIC; break; }
             if (E0 <= P.tol) { status = NMPC_STATUS_CONVERGED; break; }
             if (it >= P.max_iter) { status = NMPC_STATUS_MAX_ITER; break; }
-            if (n_cold < NMPC_COLD_RETRIES && it - it_base >= NMPC_COLD_RETRY_ITERS) { cold_retry(); break; }
-            const double mu_min = P.tol / 10.0;
-            for (;;) {
-                const double cm = fmax(fabs(cmax - mu), fabs(cmin - mu));
-                const double Emu = fmax(fmax(e_d / s_d, e_c), fmax(e_h, cm / s_c));
-                if (mu > mu_min && Emu <= 10.0 * mu) mu = fmax(mu_min, fmin(0.2 * mu, pow(mu, 1.5)));
-                else break;
-            }
+            if (ipm::cold_retry_due(lad, it)) { cold_retry(); break; }
             // wave-uniform values that live across phases go back to scalar registers (arithmetic on them runs on the vector ALU and would
             // leave them in vector registers — the ones the allocator then spills to scratch and reloads inside the hot loops)
-            mu = uni(mu);
-            const double tau = uni(fmax(0.99, 1.0 - mu));
+            mu = uni(ipm::barrier_update(mu, P.tol, e_d / s_d, e_c, e_h, cmax, cmin, s_c));
+            const double tau = uni(ipm::frac_to_boundary(mu));
             LP(1);
 
             // ---- B0. condensed stage blocks, one stage per lane, straight into LDS.  slot: v = mu/s - sigma (h - s), sigma = z/s
@@ -499,7 +491,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             __syncthreads();
             LP(2);
             // ---- B. Riccati sweep on z = (pose (3), held control (2)) with inertia correction; uniform on all lanes, stage in registers
-            double delta = uni(need_shift ? fmax(1e-20, 0.25 * delta_last) : 0.0);
+            double delta = uni(ipm::shift_first(need_shift, delta_last));
             int ntry = 0;
             bool ok;
             for (;;) {
@@ -660,14 +652,11 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
 #endif
                 if (ok) break;
                 ntry++;
-                if (delta == 0.0) delta = (delta_last == 0.0) ? 1e-4 : fmax(1e-20, delta_last / 3.0);
-                else delta *= (delta_last == 0.0) ? 100.0 : NMPC_SHIFT_ESCALATION;
-                delta = uni(delta);
-                if (delta > 1e20) break;
+                delta = uni(ipm::shift_next(delta, delta_last));      // the whole sweep is repeated
+                if (ipm::shift_exhausted(delta)) break;
             }
-            if (!ok) { if (n_cold < NMPC_COLD_RETRIES) { cold_retry(); it++; break; } status = NMPC_STATUS_NUMERIC; break; }
-            if (delta > 0.0) delta_last = delta;
-            need_shift = delta > 0.0 && (ntry > 0 || delta > 1e-6);
+            if (!ok) { if (ipm::cold_retry_left(lad)) { cold_retry(); it++; break; } status = NMPC_STATUS_NUMERIC; break; }
+            ipm::shift_accept(delta, ntry, delta_last, need_shift);
             __syncthreads();
 
             LP(3);
@@ -858,23 +847,11 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             LP(7);
             // ---- E. l1 merit backtracking (non-monotone reference: max of the last merit values of this barrier problem)
             const double theta0 = uni(th0 + thh), phi0 = uni(f - mu * lgs);
-            if (theta0 > 0.0) {
-                const double nut = fmin(dphi / ((1.0 - 0.1) * theta0), mult_max / (1.0 - 0.1));
-                nu_pen = fmax(1.0, 0.5 * nu_pen);
-                if (nu_pen < nut) nu_pen = nut + 1.0;
-                nu_pen = uni(nu_pen);
-            }
+            if (theta0 > 0.0) nu_pen = uni(ipm::penalty_update(nu_pen, dphi, theta0, mult_max));
             const double Dm = uni(dphi - nu_pen * theta0);
             double alpha = a_p, ft = f, tht = th0, ect = e_c;
-            if (mh_mu != mu || mh_nu != nu_pen) { mcount = 0; mh_mu = mu; mh_nu = nu_pen; }
-            const double m0 = uni(phi0 + nu_pen * theta0);
-            double mref = m0;
-            if (mcount > 0) mref = fmax(mref, mh0);
-            if (mcount > 1) mref = fmax(mref, mh1);
-            if (mcount > 2) mref = fmax(mref, mh2);
-            mref = uni(mref);
-            mh2 = mh1; mh1 = mh0; mh0 = m0; if (mcount < 3) mcount++;
-            const bool wd_fire = n_short >= NMPC_WATCHDOG_TRIGGER && a_p >= NMPC_WATCHDOG_MIN_AP;
+            const double mref = uni(mref_h.reference(mu, nu_pen, uni(phi0 + nu_pen * theta0)));
+            const bool wd_fire = ipm::watchdog_fires(n_short, a_p);
             bool wd_took = false;
             for (int ls = 0; ls < 30; ls++) {
                 double tb = 0.0;
@@ -906,15 +883,15 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                 const double lgt = wlogsum_(lgt_);
                 tb = wsum_(tb);
                 const double mt = (ft - mu * lgt) + nu_pen * (tht + tb);
-                if (wd_fire && isfinite(mt)) { mcount = 0; wd_took = true; break; }      // watchdog: the fraction-to-the-boundary step without the merit test
-                if (mt <= mref + 1e-4 * alpha * Dm + 1e-13 * fabs(phi0)) break;
+                if (wd_fire && isfinite(mt)) { mref_h.reset(); wd_took = true; break; }      // watchdog: the fraction-to-the-boundary step without the merit test
+                if (ipm::armijo(mt, mref, alpha, Dm, phi0)) break;
                 if (ls < 29) alpha = uni(alpha * 0.5);
                 __syncthreads();
             }
             a_d = uni(fmin(a_d, alpha));
             LP(8);
-            n_tiny = (alpha < 1e-10) ? n_tiny + 1 : 0;
-            n_short = (!wd_took && alpha < a_p) ? n_short + 1 : 0;
+            ipm::count_step(lad, alpha);
+            n_short = ipm::watchdog_count(n_short, wd_took, alpha, a_p);
             // ---- G. accept: duals and slacks (they need the old primal point), then the primal point
             auto upd = [&](double s_, double z_, double h_, double jd_, double &sn_, double &zo_) {
                 const double ds_ = jd_ + (h_ - s_), dz_ = qdiv(mu - s_ * z_ - z_ * ds_, s_);
@@ -964,9 +941,9 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             __syncthreads();
             LP(9);
             it++;
-            if (n_tiny >= 5) {
-                if (n_restart >= 3) { if (n_cold < NMPC_COLD_RETRIES) { cold_retry(); break; } status = NMPC_STATUS_STALLED; break; }
-                n_restart++; n_tiny = 0; mu = uni(fmax(mu, P.mu_init)); restarting = true;
+            if (ipm::stalled(lad)) {
+                if (ipm::restarts_used_up(lad)) { if (ipm::cold_retry_left(lad)) { cold_retry(); break; } status = NMPC_STATUS_STALLED; break; }
+                ipm::barrier_restart_begin(lad); mu = uni(ipm::restart_mu(mu, P.mu_init)); restarting = true;
                 break;
             }
         }

@@ -244,10 +244,6 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     long long tlast = clock64();
 #endif
 
-    auto lbu = [&](int c) { return (c & 1) ? -P.wmax : -P.vmax; };
-    auto bst = [&](int s) { return THB ? s : 3 * (s >> 1) + (s & 1); };            // bounded-state slot -> state index
-    auto bvl = [&](int s) { return (THB && (s % 3 == 2)) ? P.thmax : P.xymax; };
-
     // ---- column ownership: lane -> column of the augmented matrix (controls 0..NU-1, states NU..NZ-1)
     const bool is_state = tid < NX, is_ctrl = tid >= NX && tid < NZ, lvalid = tid < NZ;
     const int ms = is_state ? tid : 0;                       // my state index
@@ -261,24 +257,17 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     const int srcB = 4 * (th_lane ? 3 * mrob + 1 : (is_ctrl ? ((ma & 1) ? 3 * mrob + 2 : 3 * mrob + 1) : tid));
 
     // ---- load start, pin X_0, push into the interior of the simple bounds (IPOPT bound_push)
-    const double bp = 1e-2;
+    const Bounds bnd{P, THB};      // the simple bounds (nmpc_solve_common.h)
+    constexpr double bp = NMPC_BOUND_PUSH;
     for (int c = tid; c < NX; c += TPB) XS[c] = pp[NX + c];
     for (int e = tid; e < N1 * NX; e += TPB) {
         int k = e / NX, c = e - k * NX;
         double v = (k == 0) ? pp[c] : wi[e];
-        if (k >= 1) {
-            int d = c % 3;
-            if (d < 2 || THB) {
-                double b = (d == 2) ? P.thmax : P.xymax, px = fmin(bp * fmax(1.0, b), bp * 2.0 * b);
-                v = fmin(fmax(v, -b + px), b - px);
-            }
-        }
+        if (k >= 1) v = push_state(P, THB, c, v);
         X[e] = v; LAM[e] = 0.0; DX[e] = 0.0;     // the step is read (times a = 0) by the first merit evaluation: stale LDS may hold NaN patterns
     }
     for (int e = tid; e < N * NU; e += TPB) {
-        int c = e % NU;
-        double lo = lbu(c), hi = -lo, pu = fmin(bp * fmax(1.0, fabs(lo)), bp * (hi - lo));
-        U[e] = fmin(fmax(wi[(size_t)N1 * NX + e], lo + pu), hi - pu);
+        U[e] = bnd.push_control(e % NU, wi[(size_t)N1 * NX + e]);
         DU[e] = 0.0;
     }
     __syncthreads();
@@ -319,12 +308,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             if (P.lam_g) for (int e = tid; e < P.ng; e += TPB) P.lam_g[inst * (size_t)P.ng + e] = 0.0;      // no iteration, no multipliers: zero rows
             if (P.lam_x) for (int e = tid; e < P.nvar; e += TPB) P.lam_x[inst * (size_t)P.nvar + e] = 0.0;
             if (P.lam_p) for (int e = tid; e < 2 * NX; e += TPB) P.lam_p[inst * (size_t)(2 * NX) + e] = 0.0;
-            if (tid == 0) {
-                if (obj_out) obj_out[inst] = NAN;
-                if (status_out) status_out[inst] = NMPC_STATUS_INFEASIBLE_X0;
-                if (iters_out) iters_out[inst] = 0;
-                if (kkt_out) kkt_out[inst] = INFINITY;
-            }
+            if (tid == 0) write_result(inst, NAN, NMPC_STATUS_INFEASIBLE_X0, 0, INFINITY, obj_out, status_out, iters_out, kkt_out);
             return;
         }
     }
@@ -480,14 +464,14 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         }
         for (int e = tid; e < N * NU; e += TPB) {
             int c = e % NU;
-            double lo = lbu(c);
+            double lo = bnd.lbu(c);
             double sl = fmax(U[e] - lo, 1e-12), su = fmax(-lo - U[e], 1e-12);
             SUL[e] = sl; SUU[e] = su; ZUL[e] = mu / sl; ZUU[e] = mu / su;
         }
         for (int e = tid; e < N1 * NXB; e += TPB) {
             int k = e / NXB, s = e - k * NXB;
             if (k >= 1) {
-                double v = X[k * NX + bst(s)], b = bvl(s), sl = fmax(v + b, bp), su = fmax(b - v, bp);
+                double v = X[k * NX + bnd.bst(s)], b = bnd.bvl(s), sl = fmax(v + b, bp), su = fmax(b - v, bp);
                 ZXL[e] = mu / sl; ZXU[e] = mu / su;
             } else { ZXL[e] = 0.0; ZXU[e] = 0.0; }
         }
@@ -561,10 +545,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     double f, lgs, th0, e_c, e_h;
     double delta_last, nu_pen, kkt = INFINITY;
     bool need_shift, restarting = false, cold = false;
-    int n_cold = 0, it_base = 0;      // cold-start retries done / iteration at which the current attempt started (NMPC_COLD_RETRY_ITERS)
-    int n_tiny = 0, n_restart = 0;      // consecutive iterations with a step length below 1e-10 (stall -> restart, then NMPC_STATUS_STALLED)
-    double mh0 = 0.0, mh1 = 0.0, mh2 = 0.0, mh_mu = -1.0, mh_nu = -1.0;   // merit values of the last three iterates (same mu, nu)
-    int mcount;
+    ipm::Ladder lad;          // stall / restart ladder: tiny steps -> barrier restarts -> cold retries -> NMPC_STATUS_STALLED (nmpc_ipm.h)
+    ipm::MeritRef mref_h;     // merit values of the last three iterates (same mu, nu)
     int iter = 0, status = NMPC_STATUS_MAX_ITER;
     const double n_ineq = (double)P.n_ineq;
 
@@ -573,32 +555,12 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     // sitting on its bound would restart with a slack of ~1e-6 and a dual of mu / 1e-6), slacks return onto the constraint
     // values, duals = mu / s, multipliers = 0.  One call site for the initialisation keeps the register budget of the main loop.
     for (;;) {
-    if (restarting) {
-        if (cold) {       // the reference's cold start (C6:398-400): X_k = x0, U = 0
-            for (int e = tid + NX; e < N1 * NX; e += TPB) X[e] = X[e % NX];
-            for (int e = tid; e < N * NU; e += TPB) U[e] = 0.0;
-            cold = false;
-            __syncthreads();
-        }
-        for (int e = tid + NX; e < N1 * NX; e += TPB) {
-            const int d = (e % NX) % 3;
-            if (d < 2 || THB) {
-                double b = (d == 2) ? P.thmax : P.xymax, px = fmin(bp * fmax(1.0, b), bp * 2.0 * b);
-                X[e] = fmin(fmax(X[e], -b + px), b - px);
-            }
-            LAM[e] = 0.0;
-        }
-        for (int e = tid; e < N * NU; e += TPB) {
-            double lo = lbu(e % NU), hi = -lo, pu = fmin(bp * fmax(1.0, fabs(lo)), bp * (hi - lo));
-            U[e] = fmin(fmax(U[e], lo + pu), hi - pu);
-        }
-        __syncthreads();
-    }
+    if (restarting) { restart_point<M_, THB, TPB>(P, bnd, cold, X, U, LAM); cold = false; }
     trig();
     __syncthreads();
     init_barrier();
     merit(0.0, f, lgs, th0, e_c, e_h);
-    delta_last = 0.0; nu_pen = 1.0; need_shift = false; mcount = 0; restarting = false;
+    delta_last = 0.0; nu_pen = 1.0; need_shift = false; mref_h.reset(); restarting = false;
     PROF_T(0);
 
     for (;;) {
@@ -723,13 +685,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #endif
         e_d = wmax<TPB>(e_d, RED); lsum = wsum<TPB>(lsum, RED); zsum = wsum<TPB>(zsum, RED);
         szmax = wmax<TPB>(szmax, RED); szmin = wmin<TPB>(szmin, RED);
-        const double smax = 100.0;
-        double s_d = fmax(smax, (lsum + zsum) / ((double)(N * NX) + n_ineq)) / smax;
-        double s_c = fmax(smax, zsum / fmax(n_ineq, 1.0)) / smax;
-        double E0 = fmax(fmax(e_d / s_d, e_c), fmax(e_h, szmax / s_c));
+        const ipm::OptErr oe = ipm::opt_error(e_d, e_c, e_h, lsum, zsum, szmax, (double)(N * NX) + n_ineq, fmax(n_ineq, 1.0));
+        const double s_d = oe.s_d, s_c = oe.s_c, E0 = oe.E0;
         kkt = E0;
-        auto cold_retry = [&]() { cold = true; n_cold++; it_base = iter; restarting = true; el = n_cold >= 2; mu = P.mu_init; n_tiny = 0; n_restart = 0; };      // the second restart of last resort is the elastic phase (include/nmpc_constants.h)
-        if (!(E0 == E0)) { if (n_cold < NMPC_COLD_RETRIES && iter < P.max_iter) cold_retry(); else status = NMPC_STATUS_NUMERIC; break; }
+        auto cold_retry = [&]() { ipm::cold_retry_begin(lad, iter); cold = true; restarting = true; el = lad.n_cold >= 2; mu = P.mu_init; };      // the second restart of last resort is the elastic phase (include/nmpc_constants.h)
+        if (!(E0 == E0)) { if (ipm::cold_retry_left(lad) && iter < P.max_iter) cold_retry(); else status = NMPC_STATUS_NUMERIC; break; }
         if (E0 <= P.tol) {
             status = NMPC_STATUS_CONVERGED;
             if (el) {       // the penalty problem's solution solves the NLP only if every elastic variable has closed
@@ -741,16 +701,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             break;
         }
         if (iter >= P.max_iter) { status = NMPC_STATUS_MAX_ITER; break; }
-        if (n_cold < NMPC_COLD_RETRIES && iter - it_base >= NMPC_COLD_RETRY_ITERS) { cold_retry(); break; }
-        const double mu_min = P.tol / 10.0;
+        if (ipm::cold_retry_due(lad, iter)) { cold_retry(); break; }
         const double mu_packs = mu;      // the barrier parameter the fused pass wrote the stage packs with
-        for (;;) {
-            double cm = fmax(fabs(szmax - mu), fabs(szmin - mu));
-            double Emu = fmax(fmax(e_d / s_d, e_c), fmax(e_h, cm / s_c));
-            if (mu > mu_min && Emu <= 10.0 * mu) mu = fmax(mu_min, fmin(0.2 * mu, pow(mu, 1.5)));
-            else break;
-        }
-        const double tau = fmax(0.99, 1.0 - mu);
+        mu = ipm::barrier_update(mu, P.tol, e_d / s_d, e_c, e_h, szmax, szmin, s_c);
+        const double tau = ipm::frac_to_boundary(mu);
         PROF_T(1);
 
         // ============ B0. stage packs: everything of stage k that does not depend on the cost-to-go
@@ -824,7 +778,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         // Partial re-factorisation (round 4, include/nmpc_constants.h): the cost-to-go entering every NMPC_CKPT_EVERY-th stage is saved in the
         // workspace; a rejected pivot at stage kf escalates the shift and resumes the sweep at the saved stage NMPC_RESUME_STAGE(kf, N) — the
         // stages above keep their factorisation (the pivot rows already stored) and the smaller shift it was made with.
-        double delta = need_shift ? fmax(1e-20, 0.25 * delta_last) : 0.0;
+        double delta = ipm::shift_first(need_shift, delta_last);
         int ntry = 0;
         bool ok;
         int kst = N - 1;        // stage this pass of the sweep starts at
@@ -1221,14 +1175,12 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             }
             if (ok) break;
             ntry++;
-            if (delta == 0.0) delta = (delta_last == 0.0) ? 1e-4 : fmax(1e-20, delta_last / 3.0);
-            else delta *= (delta_last == 0.0) ? 100.0 : NMPC_SHIFT_ESCALATION;
-            if (delta > 1e20) break;
+            delta = ipm::shift_next(delta, delta_last);
+            if (ipm::shift_exhausted(delta)) break;
             kst = NMPC_RESUME_STAGE(kf, N);        // (wave 0's: the other waves of the latency shape do not sweep)
         }
-        if (!ok) { if (n_cold < NMPC_COLD_RETRIES) { cold_retry(); iter++; } else status = NMPC_STATUS_NUMERIC; break; }
-        if (delta > 0.0) delta_last = delta;
-        need_shift = delta > 0.0 && (ntry > 0 || delta > 1e-6);
+        if (!ok) { if (ipm::cold_retry_left(lad)) { cold_retry(); iter++; } else status = NMPC_STATUS_NUMERIC; break; }
+        ipm::shift_accept(delta, ntry, delta_last, need_shift);
         __syncthreads();   // s_waitcnt vmcnt(0): the stage-0 gains were stored a moment ago by other lanes of this wave
         PROF_T(3);
 
@@ -1404,12 +1356,12 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         };
         for (int e = tid_local(); e < N * NU; e += TPB) {
             int c = e % NU;
-            double lo = lbu(c), u = U[e], du = DU[e], sl = SUL[e], su = SUU[e];
+            double lo = bnd.lbu(c), u = U[e], du = DU[e], sl = SUL[e], su = SUU[e];
             fb(sl, ZUL[e], du + ((u - lo) - sl)); fb(su, ZUU[e], -du + ((-lo - u) - su));
         }
         for (int e = tid_local(); e < N * NXB; e += TPB) {
             int k = 1 + e / NXB, s = e - (k - 1) * NXB;
-            double v = X[k * NX + bst(s)], dv = DX[k * NX + bst(s)], b = bvl(s), sl = v + b, su = b - v;
+            double v = X[k * NX + bnd.bst(s)], dv = DX[k * NX + bnd.bst(s)], b = bnd.bvl(s), sl = v + b, su = b - v;
             fb(sl, ZXL[k * NXB + s], dv + ((v + b) - sl)); fb(su, ZXU[k * NXB + s], -dv + ((b - v) - su));
         }
         auto step_length_rows = [&](auto elc) {
@@ -1539,31 +1491,20 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         dphi -= mu * dphi_b;
         dphi = wsum<TPB>(dphi, RED);
         const double phi0 = f - mu * lgs;
-        if (th0 > 0.0) {
-            // Nocedal-Wright (18.36), rho = 0.1; capped by the multiplier norm it cannot exceed in exact arithmetic
-            double nut = fmin(dphi / ((1.0 - 0.1) * th0), mult_max / (1.0 - 0.1));
-            nu_pen = fmax(1.0, 0.5 * nu_pen);      // the penalty may relax again: one bad step must not cripple the rest of the solve
-            if (nu_pen < nut) nu_pen = nut + 1.0;
-        }
+        if (th0 > 0.0) nu_pen = ipm::penalty_update(nu_pen, dphi, th0, mult_max);
         const double Dm = dphi - nu_pen * th0;
         double alpha = a_p, ft, lgt, tht, ect, eht;
         // non-monotone (Grippo-type) reference value: max of the current and the last three merit values of this barrier problem
-        if (mh_mu != mu || mh_nu != nu_pen) { mcount = 0; mh_mu = mu; mh_nu = nu_pen; }
-        const double m0 = phi0 + nu_pen * th0;
-        double mref = m0;
-        if (mcount > 0) mref = fmax(mref, mh0);
-        if (mcount > 1) mref = fmax(mref, mh1);
-        if (mcount > 2) mref = fmax(mref, mh2);
-        mh2 = mh1; mh1 = mh0; mh0 = m0; if (mcount < 3) mcount++;
+        const double mref = mref_h.reference(mu, nu_pen, phi0 + nu_pen * th0);
         for (int ls = 0; ls < 30; ls++) {
             merit(alpha, ft, lgt, tht, ect, eht);
-            if ((ft - mu * lgt) + nu_pen * tht <= mref + 1e-4 * alpha * Dm + 1e-13 * fabs(phi0)) break;
+            if (ipm::armijo((ft - mu * lgt) + nu_pen * tht, mref, alpha, Dm, phi0)) break;
             if (ls < 29) alpha *= 0.5;
         }
         // the duals never step further than the primal variables actually moved: a dual step taken
         // without its primal counterpart (line search cut alpha) blows up the dual infeasibility of rows with tiny slacks
         a_d = fmin(a_d, alpha);
-        n_tiny = (alpha < 1e-10) ? n_tiny + 1 : 0;
+        ipm::count_step(lad, alpha);
         PROF_T(6);
 #ifdef NMPC_PROFILE
         if (prof_out && tid == 0 && (int)inst == P.trace_inst && iter < 2040) {
@@ -1598,14 +1539,14 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         };
         for (int e = tid_local(); e < N * NU; e += TPB) {
             int c = e % NU;
-            double lo = lbu(c), u = U[e], du = DU[e], sl = SUL[e], su = SUU[e], sn;
+            double lo = bnd.lbu(c), u = U[e], du = DU[e], sl = SUL[e], su = SUU[e], sn;
             ZUL[e] = zup(sl, ZUL[e], du + ((u - lo) - sl), sn); SUL[e] = sn;
             ZUU[e] = zup(su, ZUU[e], -du + ((-lo - u) - su), sn); SUU[e] = sn;
         }
         for (int e = tid_local(); e < N * NXB; e += TPB) {
             int k = 1 + e / NXB, s = e - (k - 1) * NXB;
             const int es = k * NXB + s;
-            double v = X[k * NX + bst(s)], dv = DX[k * NX + bst(s)], b = bvl(s), sl = v + b, su = b - v, sn;
+            double v = X[k * NX + bnd.bst(s)], dv = DX[k * NX + bnd.bst(s)], b = bnd.bvl(s), sl = v + b, su = b - v, sn;
             ZXL[es] = zup(sl, ZXL[es], dv + ((v + b) - sl), sn);
             ZXU[es] = zup(su, ZXU[es], -dv + ((b - v) - su), sn);
         }
@@ -1645,10 +1586,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         f = ft; lgs = lgt; th0 = tht; e_c = ect; e_h = eht;
         iter++;
         PROF_T(8);
-        if (n_tiny >= 5) {
-            if (n_restart >= 3) { if (n_cold < NMPC_COLD_RETRIES) cold_retry(); else status = NMPC_STATUS_STALLED; break; }
-            n_restart++; n_tiny = 0;
-            mu = fmax(mu, P.mu_init);
+        if (ipm::stalled(lad)) {
+            if (ipm::restarts_used_up(lad)) { if (ipm::cold_retry_left(lad)) cold_retry(); else status = NMPC_STATUS_STALLED; break; }
+            ipm::barrier_restart_begin(lad);
+            mu = ipm::restart_mu(mu, P.mu_init);
             restarting = true;
             break;
         }
@@ -1707,12 +1648,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             for (int e = tid; e < Ne * NU; e += TPB) lx[N1e * NX + e] = zuu[e] - zul[e];
         }
     }
-    if (tid == 0) {
-        if (obj_out) obj_out[inst] = f;
-        if (status_out) status_out[inst] = status;
-        if (iters_out) iters_out[inst] = iter;
-        if (kkt_out) kkt_out[inst] = kkt;
-    }
+    if (tid == 0) write_result(inst, f, status, iter, kkt, obj_out, status_out, iters_out, kkt_out);
 #ifdef NMPC_PROFILE
     if (tid == 0 && prof_out) for (int i = 0; i < 12; i++) atomicAdd((unsigned long long *)&prof_out[i], (unsigned long long)prof[i]);
 #endif

@@ -1,5 +1,9 @@
-// nmpc_solve_common.h — geometry, pinned-order arithmetic helpers and wave primitives shared by the LDS-resident solve kernels
-// (nmpc_solve_lds.hip: element-per-lane Riccati stage; nmpc_solve_col.hip: column-per-lane, register-resident Riccati stage).
+// nmpc_solve_common.h — geometry, wave primitives and the start / restart / exit text shared by the three swarm solve kernels (nmpc_kernels.hip:
+// HBM-resident; nmpc_solve_lds.hip: element-per-lane Riccati stage; nmpc_solve_col.hip: column-per-lane, register-resident Riccati stage), and
+// the pinned-order arithmetic helpers of the two LDS-resident ones.  The scalar controller of the iteration is nmpc_ipm.h.
+// NOT shared, on purpose: kernel 1 keeps its own constraint arithmetic (slot_h, slot_jd, jxT_robot and its stage-0 pre-check in nmpc_kernels.hip),
+// which rounds differently from the fma-pinned h_pair / h_obs below — unifying it would move kernel 1's results; init_barrier, merit, the
+// stage-parallel phases and the sweeps belong to each kernel's data layout and stay there.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -8,6 +12,7 @@
 #include <type_traits>
 
 #include "nmpc_device.h"
+#include "nmpc_ipm.h"
 
 namespace nmpc {
 
@@ -253,6 +258,76 @@ template <int TPB> __device__ __forceinline__ double wmax(double v, double *red)
     return uniform_f64(v);
 }
 template <int TPB> __device__ __forceinline__ double wmin(double v, double *red) { return -wmax<TPB>(-v, red); }
+
+// ---- the simple bounds of the swarm NLP (C6:349-352); thb: the heading is bounded as well (kernel 1 passes P.thb, the others their THB)
+__device__ __forceinline__ double lbu(const KParams &P, int c) { return (c & 1) ? -P.wmax : -P.vmax; }      // lower bound of control c (the upper one is its negative)
+__device__ __forceinline__ int bst(int thb, int s) { return thb ? s : 3 * (s >> 1) + (s & 1); }             // bounded-state slot -> state index
+__device__ __forceinline__ double bvl(const KParams &P, int thb, int s) { return (thb && (s % 3 == 2)) ? P.thmax : P.xymax; }
+constexpr double NMPC_BOUND_PUSH = 1e-2;      // IPOPT bound_push = bound_frac
+// push control c into the interior of its bounds (state component: push_state below)
+__device__ __forceinline__ double push_control(const KParams &P, int c, double v)
+{
+    constexpr double bp = NMPC_BOUND_PUSH;
+    double lo = lbu(P, c), hi = -lo, pu = fmin(bp * fmax(1.0, fabs(lo)), bp * (hi - lo));
+    return fmin(fmax(v, lo + pu), hi - pu);
+}
+// ... as the LDS-resident kernels hold them: a reference and the flag, the shape of the closures this replaces.  lbu, bvl and push_control
+// repeat the bodies above on purpose: forwarding to the free functions changes how the column kernel reaches the bound constants (scalar
+// loads) and four of its symbols then gain scratch (docs/IPM_CONTROL.md).
+struct Bounds {
+    const KParams &P;
+    const int thb;
+    __device__ __forceinline__ double lbu(int c) const { return (c & 1) ? -P.wmax : -P.vmax; }
+    __device__ __forceinline__ int bst(int s) const { return nmpc::bst(thb, s); }
+    __device__ __forceinline__ double bvl(int s) const { return (thb && (s % 3 == 2)) ? P.thmax : P.xymax; }
+    __device__ __forceinline__ double push_control(int c, double v) const
+    {
+        constexpr double bp = NMPC_BOUND_PUSH;
+        double lo = lbu(c), hi = -lo, pu = fmin(bp * fmax(1.0, fabs(lo)), bp * (hi - lo));
+        return fmin(fmax(v, lo + pu), hi - pu);
+    }
+};
+// push state component c of a stage into the interior of its bounds.  Both bounds are read before the choice between them: written as
+// (d == 2) ? P.thmax : P.xymax the choice becomes one between two addresses and the load a vector load from the parameter block.
+__device__ __forceinline__ double push_state(const KParams &P, int thb, int c, double v)
+{
+    constexpr double bp = NMPC_BOUND_PUSH;
+    const int d = c % 3;
+    const double thmax = P.thmax, xymax = P.xymax;
+    if (d < 2 || thb) {
+        double b = (d == 2) ? thmax : xymax, px = fmin(bp * fmax(1.0, b), bp * 2.0 * b);
+        v = fmin(fmax(v, -b + px), b - px);
+    }
+    return v;
+}
+// The primal point of a (re)start of the barrier iteration in the LDS-resident kernels: cold — the reference's cold start X_k = x0, U = 0
+// (C6:398-400) — or the current point; either way pushed strictly inside the simple bounds (a control sitting on its bound would restart with
+// a slack of ~1e-6 and a dual of mu / 1e-6), multipliers 0.  Slacks and duals follow in each kernel's init_barrier.
+template <int M_, int THB, int TPB> __device__ __forceinline__ void restart_point(const KParams &P, const Bounds &bnd, bool cold, double *X, double *U, double *LAM)
+{
+    constexpr int NX = 3 * M_, NU = 2 * M_;
+    const int tid = threadIdx.x, N = P.N, N1 = P.N + 1;
+    if (cold) {
+        for (int e = tid + NX; e < N1 * NX; e += TPB) X[e] = X[e % NX];
+        for (int e = tid; e < N * NU; e += TPB) U[e] = 0.0;
+        __syncthreads();
+    }
+    for (int e = tid + NX; e < N1 * NX; e += TPB) {
+        X[e] = push_state(P, THB, e % NX, X[e]);
+        LAM[e] = 0.0;
+    }
+    for (int e = tid; e < N * NU; e += TPB) U[e] = bnd.push_control(e % NU, U[e]);
+    __syncthreads();
+}
+// what a solve reports per instance (one thread writes it): the infeasible-x0 exit and the normal exit of every swarm kernel
+__device__ __forceinline__ void write_result(size_t inst, double obj, int status, int iters, double kkt, double *obj_out, int32_t *status_out, int32_t *iters_out,
+                                             double *kkt_out)
+{
+    if (obj_out) obj_out[inst] = obj;
+    if (status_out) status_out[inst] = status;
+    if (iters_out) iters_out[inst] = iters;
+    if (kkt_out) kkt_out[inst] = kkt;
+}
 
 // Sum of log(s_i), s_i > 0, accumulated as (product of the mantissas, sum of the exponents): four instructions per term instead of a
 // logarithm (~90), one logarithm per wavefront at the end.  The mantissa product is renormalised after every term (no underflow however

@@ -4,9 +4,11 @@
     python tools/ab_outputs.py --compare a.npz b.npz         lists the arrays whose bit patterns differ (exit status 1 if any)
     python tools/ab_outputs.py --compare-dumps dirA dirB     the same for two `bench.py --dump-outputs` directories
 Cases: the ten shapes of tests/test_gpu_phase_passes.py (plain call and with multipliers), the elastic / cold-retry fixtures of the composite
-and the moving-obstacle rescue fixtures (per-instance field) on pins 3, 4, 5, and nmpc_solve_batch_duals on the six-robot bench batch.  After
-each solve the handle's workspace is recorded too, as one sha256 per instance (`<case>/ws`): a changed scratch value shows even where no
-output moved.  NaN payloads count: arrays are compared as raw bytes."""
+on every pin (1 .. 5: they walk the barrier restarts, both cold retries and the elastic phase of all three swarm kernels), the moving-obstacle
+rescue fixtures (per-instance field) on pins 3, 4, 5, nmpc_solve_batch_duals on the six-robot bench batch, every kernel-1 and kernel-2 row of
+tests/kernel_variants.TABLE by its own recipe, and the LIDAR kernel: one recipe of tests/lidar_variants.TABLE per instantiation and
+LIDAR_BENCH_PICK of its bench batch.  After each swarm solve the handle's workspace is recorded too, as one sha256 per instance (`<case>/ws`):
+a changed scratch value shows even where no output moved.  NaN payloads count: arrays are compared as raw bytes."""
 import ctypes as C
 import hashlib
 import os
@@ -43,14 +45,60 @@ def workspace_hashes(s, B):
     return out
 
 
-def record(out, name, s, P, W, **kw):
+def record(out, name, s, P, W, ws=True, **kw):
     import torch
     r = s.solve_batch(P, W, **kw)
     torch.cuda.synchronize()
     for k, v in r.items():
         out["%s/%s" % (name, k)] = v.cpu().numpy()
-    out[name + "/ws"] = workspace_hashes(s, len(P))
+    if ws:
+        out[name + "/ws"] = workspace_hashes(s, len(P))
     print("%-52s status %s iterations %d..%d" % (name, sorted(set(out[name + "/status"].tolist())), out[name + "/iters"].min(), out[name + "/iters"].max()), flush=True)
+
+
+# Instances of the LIDAR bench batch (lidar_bench_batch below, 4096 instances), chosen on the CPU from the oracle's per-iteration trace
+# (NMPC_LIDAR_ORACLE_TRACE): the watchdog of the line search fires, once or twice, in the first LIDAR_WATCHDOG of them (ten successive
+# shortened steps, then a step of fraction-to-the-boundary length >= 0.5 taken as it is; they are among the 55 longest solves of the batch,
+# 45 .. 60 iterations); the rest are the first sixteen instances of the batch.
+# Traced were the 64 longest solves of the batch, not all 4096: none of those takes a barrier restart on the oracle (no five successive steps
+# below 1e-10), so none is picked for one; whether a shorter solve of the batch does is not known.  The restart ladder of the LIDAR kernel is
+# walked by its parity tests.
+LIDAR_BENCH_PICK = [1985, 88, 1345, 222, 899, 3625, 2352, 141, 2303, 2883, 3786, 3853, 3584, 3316, 1905, 3005, 976, 4011, 3643, 2600, 1793, 2498, 64, 2518, 1998, 1524, 232, 3899, 1437, 3670, 1898, 1922, 3949, 3716, 737, 2270, 980, 996, 1314, 3287, 2060, 2050, 367, 1283, 238, 806, 2609, 733, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15]
+LIDAR_WATCHDOG = 48
+
+
+def lidar_bench_batch(B=4096):
+    """the LIDAR batch of bench.py --full and tools/bench_lidar.py (same generator and seed), with the scan made on the CPU"""
+    from oracle import lidar_ref as LR
+    lc = LR.lidar_v4()
+    rng = np.random.Generator(np.random.PCG64(20210146))
+    P, W = [], []
+    for _ in range(B):
+        pose = np.array([rng.uniform(0.0, 0.15), rng.uniform(0.0, 0.15), rng.uniform(0.4, 1.1)])
+        world = [(float(rng.uniform(0.8, 2.6)), float(rng.uniform(0.3, 2.4)), float(rng.uniform(0.15, 0.3))) for _ in range(3)]
+        scan = LR.scan_of_world(pose, world, lc.R)
+        P.append(LR.make_p(lc, pose, np.array([3.0, 2.5, 0.0]) + rng.uniform(-0.3, 0.3, 3), scan)); W.append(LR.cold_start(lc, np.concatenate([pose, scan])))
+    return lc, np.stack(P), np.stack(W)
+
+
+def run_lidar(out):
+    import nmpc_amd
+    from oracle import lidar_ref as LR
+    from tests import lidar_variants as LV
+    from tests.test_gpu_lidar import _product
+    from tests.test_gpu_lidar_variants import _two_wave_threshold
+
+    def solver(cfg, max_iter, B):
+        lbx, ubx, _, _ = LR.bounds(cfg)
+        return nmpc_amd.LidarSolver(_product(cfg, max_iter=max_iter), lbx=lbx, ubx=ubx, max_batch=B)
+    for inst in ((-1, 1), (10, 1), (10, 2)):      # the first recipe of each instantiation with a horizon of nine stages or more
+        r = next(r for r in LV.TABLE if r.inst == inst and r.N >= 8 and r.R > 0)
+        B = _two_wave_threshold() + 1 if r.B is None else r.B
+        cfg, P, W = LV.inputs(r, B)
+        record(out, "lidar_" + LV.row_id(r), solver(cfg, r.max_iter, B), P, W, ws=False)
+    lc, P, W = lidar_bench_batch()
+    P, W = P[LIDAR_BENCH_PICK], W[LIDAR_BENCH_PICK]
+    record(out, "lidar_bench_pick", solver(lc, 2000, len(P)), P, W, ws=False)
 
 
 def run(path):
@@ -68,7 +116,7 @@ def run(path):
     gold = os.path.join(ROOT, "tests", "golden")
     for f in ("elastic_cases", "cold_retry_cases", "cold_retry_cases2"):
         z = np.load(os.path.join(gold, f + ".npz"))
-        for pin in (3, 4, 5):
+        for pin in (1, 2, 3, 4, 5):
             s = nmpc_amd.NmpcSolver(Hh.to_product_cfg(oc, max_iter=2000), max_batch=len(z["p"]), kernel=pin)
             record(out, "%s_pin%d" % (f, pin), s, z["p"], z["w"])
     z = np.load(os.path.join(gold, "moving_obstacle_cases.npz"))
@@ -77,6 +125,14 @@ def run(path):
         record(out, "moving_obstacle_cases_pin%d" % pin, s, z["p"], z["w"], obstacles=z["obs"])
     oc, B, P, W0 = Hh.bench_batch("six", 64)
     record(out, "bench_six_64_duals", nmpc_amd.NmpcSolver(Hh.to_product_cfg(oc, max_iter=2000), max_batch=B), P, W0, want_duals=True)
+    from tests import kernel_variants as KV
+    for r in KV.TABLE:
+        if r.row[0] in (1, 2):      # the HBM-resident and the element-per-lane kernel: short cold solves at the recipes' batch sizes
+            cfg, P, W0, F = KV.inputs(r)
+            s = nmpc_amd.NmpcSolver(Hh.to_product_cfg(cfg, max_iter=r.max_iter), max_batch=r.B, kernel=r.pin)
+            assert int(s.kernel_for_batch(r.B)) == r.row[0], (r.row, s.kernel_for_batch(r.B))
+            record(out, KV.row_id(r), s, P, W0)
+    run_lidar(out)
     np.savez_compressed(path, **out)
     print("%d arrays of %s -> %s" % (len(out), nmpc_amd._lib.SO_PATH, path))
 
