@@ -850,6 +850,9 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #pragma unroll
             for (int t = 0; t < PKR; t++) { int e = tid + t * TPB; pkr[t] = (FULL || e < G::PACK) ? gpack[(size_t)kst * G::PACK + e] : 0.0; }
             double pend_row = 0.0, pend_rhs = 0.0;
+            // the lane that stores the right-hand side of a pivot row (times -1/pivot) is the one that forms it: the diagonal's lane of control rcol
+            const bool rhs_lane = c_ctrl && rh == rw;
+            const int rhs_row = rcol;
             int ckc = 0;        // stages since the last saved one (the pass starts at a saved stage, or at N-1)
 #if NMPC_COL_DUMMY_ST
             // vmcnt counts loads and stores in issue order.  The wait for a stage's pack (requested at the top of the previous stage) may leave
@@ -874,7 +877,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 double *const gkrow = gkt + (size_t)k * G::KTS + ((cvalid && rh == 0) ? rcol : NZ + 1);
                 if (k < kst) {
                     gkrow[G::KTS + (NU - 1) * G::LDC] = pend_row;
-                    if (tid < NU) gkt[(size_t)(k + 1) * G::KTS + tid * G::LDC + NZ] = pend_rhs;
+                    if (rhs_lane) gkt[(size_t)(k + 1) * G::KTS + rhs_row * G::LDC + NZ] = pend_rhs;
                 }
                 if (ckc == NMPC_CKPT_EVERY) {      // save the cost-to-go entering this stage: state rows and right-hand side as the lanes hold them
                     ckc = 0;
@@ -930,22 +933,31 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 PROF_T(10);
                 // ---- 5. NU pivot steps in natural control order.  Pivot j is row (half hj, slot ij); its diagonal sits on lane 48 hj + ij,
                 //      the right-hand side of column j on lane 16 hj + ij of the lower half.  The pivot test runs on the lanes
-                //      themselves (thr = 1e-9 |diagonal as assembled| on the lane that holds the diagonal of its column) and the
-                //      reciprocal — or -1 for a rejected pivot — is read from the diagonal's lane; a rejected pivot does not leave the
-                //      stage early (the rest of the stage computes garbage that the retry overwrites): no branch per pivot
+                //      themselves (thr = 1e-9 |diagonal as assembled| on the lane that holds the diagonal of its column): the verdict is
+                //      the diagonal lane's bit of the compare mask, and the reciprocal, read from that lane, is whatever it comes to for
+                //      a rejected pivot; a rejected pivot does not leave the stage early (the rest of the stage computes garbage that the
+                //      retry overwrites — pivot rows and right-hand sides; the saved cost-to-go is stored before the pivots): no
+                //      branch per pivot, no select and no compare on the reciprocal (docs/PIVOT_STEP.md)
                 double thr = 0.0;
                 static_for<0, NC>([&](auto ic) { constexpr int i = decltype(ic)::value; thr = (rh == rw && rn == i) ? m[i] : thr; });
                 thr = 1e-9 * fabs(thr);
-                auto pivot_inv = [&](double d) { return (d > thr) ? rcp_nr(d) : -1.0; };      // thr >= 0 (or NaN, which rejects): d > thr already says d > 0
-                double inv_cur = lane_read(pivot_inv(m[rp_slot(0)]), 48 * rp_half(0) + rp_slot(0));
+                unsigned long long rej = 0;              // bit 48 hj + ij: pivot j failed the test (scalar registers)
+                double rcv;                              // reciprocals of the current pivot's register, lane by lane
+                auto pivot_inv = [&](auto jc) {
+                    constexpr int dl = 48 * rp_half(decltype(jc)::value) + rp_slot(decltype(jc)::value);
+                    const double d = m[rp_slot(decltype(jc)::value)];
+                    rej |= ~__builtin_amdgcn_ballot_w64(d > thr) & (1ull << dl);      // thr >= 0 (or NaN, which rejects): d > thr already says d > 0
+                    rcv = rcp_nr(d);
+                    return lane_read(rcv, dl);
+                };
+                double inv_cur = pivot_inv(std::integral_constant<int, 0>{});
                 double rhsv = 0.0;
-                bool okk = true;
                 static_for<0, NU>([&](auto jc) {
                     constexpr int j = decltype(jc)::value, hj = rp_half(j), ij = rp_slot(j);
                     const double inv = inv_cur;
-                    okk = okk && (inv > 0.0);
                     const double rhs_j = lane_read(m[RR], 16 * hj + ij);
-                    rhsv = (tid == j) ? -rhs_j * inv : rhsv;
+                    // the diagonal's lane holds both factors of the row's right-hand side: m[RR] (both halves carry that row) and the reciprocal
+                    rhsv = (tid == 48 * hj + ij) ? -m[RR] * rcv : rhsv;
                     // own = the pivot row on every lane's own column, in both halves.  The swap leaves the OTHER row of the register in
                     // both halves of m[ij]: the pivot row itself is dead from here on, the other one keeps its place
                     double own = m[ij];
@@ -966,7 +978,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     auto elim = [&](auto ac) { constexpr int i = decltype(ac)::value; fmac_rowb<i>(m[i], ur, nrjv); };
                     if constexpr (j + 1 < NU) {       // the next pivot row first: its reciprocal overlaps the other rows
                         elim(std::integral_constant<int, rp_slot(j + 1)>{});
-                        inv_cur = lane_read(pivot_inv(m[rp_slot(j + 1)]), 48 * rp_half(j + 1) + rp_slot(j + 1));
+                        inv_cur = pivot_inv(std::integral_constant<int, j + 1>{});
                     }
                     // a control register stays live while one of its two rows has not been a pivot yet
                     static_for<0, RR>([&](auto ac) {
@@ -975,13 +987,13 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     });
                     m[RR] = fma(-rhs_j, rjv, m[RR]);
                 });
-                ok = okk;
+                ok = rej == 0;
                 PROF_T(11);
                 if (!ok) { kf = k; break; }
                 pend_rhs = rhsv;
                 if (k == 0) {
                     gkrow[(NU - 1) * G::LDC] = pend_row;
-                    if (tid < NU) gkt[tid * G::LDC + NZ] = pend_rhs;
+                    if (rhs_lane) gkt[rhs_row * G::LDC + NZ] = pend_rhs;
                 }
             }
             } else {
