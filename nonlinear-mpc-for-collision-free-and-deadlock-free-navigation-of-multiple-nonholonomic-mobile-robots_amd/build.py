@@ -25,7 +25,7 @@ COL_UNITS = [(1, 5, 0), (6, 8, 0), (9, 10, 0), (1, 5, 1), (6, 8, 1), (9, 10, 1)]
 UNITS = [(s, s.rsplit(".", 1)[0], []) for s in SOURCES if s != "nmpc_solve_col.hip"] \
     + [("nmpc_solve_col.hip", "nmpc_solve_col_p%d" % (k + 1), ["-DNMPC_COL_UNIT=%d,%d,%d" % u] + (["-DNMPC_COL_ENTRY"] if k == 0 else []))
        for k, u in enumerate(COL_UNITS)]
-DEPS = SOURCES + ["nmpc_device.h", "nmpc_solve_common.h", "nmpc_ipm.h"] + [os.path.join("..", "..", "include", h) for h in ("nmpc.h", "nmpc_lidar.h", "nmpc_constants.h", "nmpc_debug.h")]
+DEPS = SOURCES + ["nmpc_device.h", "nmpc_solve_common.h", "nmpc_ipm.h", "nmpc_wave.h"] + [os.path.join("..", "..", "include", h) for h in ("nmpc.h", "nmpc_lidar.h", "nmpc_constants.h", "nmpc_debug.h")]
 
 
 def _hipcc() -> str:

@@ -107,24 +107,10 @@ static void fill_params(const nmpc_config_t *c, nmpc::KParams *P)
     P->oSN = take((int64_t)N * m); P->oCS = take((int64_t)N * m); P->oC = take(nX); P->oH = take(nH); P->oGX = take(nX);
     P->oHUU = take(nU); P->oGU = take(nU); P->oHVT = take((int64_t)N * m); P->oHTT = take((int64_t)N * m);
     P->oKG = take((int64_t)N * nu * nx); P->oKFF = take(nU);
-    P->oEL = take(2 * nH);  // elastic variables of the HBM-resident kernel and their steps (one per inequality slot; only the pair / obstacle slots are used)
-    P->oCKP = take((int64_t)((N - 1) / NMPC_CKPT_EVERY + 1) * (nx * nx + nx));      // saved cost-to-go of the backward sweep (partial re-factorisation)
+    P->oEL = take(2 * nmpc::HbmWs::el_half(N, P->nh));  // elastic variables of the HBM-resident kernel and their steps (one per inequality slot; only the pair / obstacle slots are used)
+    P->oCKP = take((int64_t)((N - 1) / NMPC_CKPT_EVERY + 1) * nmpc::HbmWs::ckpt_slot(nx));      // saved cost-to-go of the backward sweep (partial re-factorisation)
     P->stride = o;
-    nmpc::lds_kernel_workspace(*P, m, &P->oPACK, &P->oKT, &P->stride2);
-    // slack / dual arrays of the column kernel: pair, obstacle, control-bound (slacks + duals) and state-bound (duals) rows
-    P->oDUAL = P->stride2;
-    P->stride2 += (nmpc::col_dual_doubles(*P, m) + 15) / 16 * 16;
-    {   // cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep (partial re-factorisation after a rejected pivot): the column
-        // kernel stores its registers lane by lane, (3m + 1) x 64 doubles per slot; the element-per-lane kernel its [P | p] (smaller)
-        const int64_t slots = (N - 1) / NMPC_CKPT_EVERY + 1;
-        P->oCKPT = P->stride2;
-        P->stride2 += slots * (3 * m + 1) * 64;
-    }
-    {   // elastic variables t of the pair and obstacle rows (elastic phase only)
-        const int64_t el = (int64_t)(N + 1) * (m * (m - 1) / 2 + m * K);
-        P->oELAS = P->stride2;
-        P->stride2 += (el + 15) / 16 * 16;
-    }
+    nmpc::lds_workspace_fill(P, m);
 }
 
 // the checks of nmpc_create_opts on a configuration and its options

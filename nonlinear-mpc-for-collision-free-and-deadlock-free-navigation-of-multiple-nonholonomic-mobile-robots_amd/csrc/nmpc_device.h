@@ -43,10 +43,16 @@ struct KParams {
     double *lam_g, *lam_x, *lam_p;      // per call (column kernel, nmpc_*_batch_duals): the multipliers of the returned point, [B][ng] / [B][nvar] / [B][2 nx], each or all nullptr
     int64_t stride2;      // workspace stride of the LDS-resident kernel (stage packs + transposed gains)
     int64_t oPACK, oKT;
-    int64_t oCKPT;        // LDS-resident kernels: cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep, [(N-1)/NMPC_CKPT_EVERY + 1] slots of (3m + 1) * 64 doubles
-    int64_t oELAS;        // LDS-resident kernels: elastic variables t of the pair and obstacle rows, [(N+1) * (NP + m K)]: touched only in the elastic phase
+    int64_t oCKPT;        // LDS-resident kernels: cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep, WsLayout::ckpt_slots(N) slots of WsLayout::CKPT_SLOT doubles
+    int64_t oELAS;        // LDS-resident kernels: elastic variables t of the pair and obstacle rows, WsLayout::el_pair + el_obs: touched only in the elastic phase
     int64_t oDUAL;        // column kernel: slacks and duals of the inequality rows (touched by the stage-parallel phases only) live here, not in LDS
-    int32_t oX, oU, oLAM, oS, oZ, oDX, oDU, oLAMN, oDS, oDZ, oSN, oCS, oC, oH, oGX, oHUU, oGU, oHVT, oHTT, oKG, oKFF, oCKP, oEL;      // oCKP: the HBM-resident kernel's saved cost-to-go, [(N-1)/NMPC_CKPT_EVERY + 1][nx * nx + nx]; oEL: its elastic variables, one per inequality slot
+    int32_t oX, oU, oLAM, oS, oZ, oDX, oDU, oLAMN, oDS, oDZ, oSN, oCS, oC, oH, oGX, oHUU, oGU, oHVT, oHTT, oKG, oKFF, oCKP, oEL;      // oCKP: the HBM-resident kernel's saved cost-to-go, [(N-1)/NMPC_CKPT_EVERY + 1][HbmWs::ckpt_slot]; oEL: its elastic variables and their steps, 2 x HbmWs::el_half
+};
+
+// The two places where the HBM-resident kernel's workspace (carved up by fill_params, the offsets above) has structure inside an array
+struct HbmWs {
+    static constexpr int ckpt_slot(int nx) { return nx * nx + nx; }                       // oCKP: one slot holds the saved cost-to-go [P | p]
+    static constexpr int64_t el_half(int N, int nh) { return (int64_t)(N + 1) * nh; }     // oEL: the elastic variables t, one per inequality slot, then their steps
 };
 
 // The pose reference of the cost as eval_kernel and kkt_residual_kernel read it, sum_k (X_k - xs_k)' Q (X_k - xs_k): instance b's rows start at
@@ -88,8 +94,7 @@ hipError_t launch_solve_lds(const KParams &P, const SolveVariant &v, int B, cons
 hipError_t launch_solve_col(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st);
 size_t lds_kernel_bytes(const KParams &P, int m);                 // the element-per-lane kernel's throughput shape
 size_t col_kernel_bytes(const KParams &P, int m, int shape);      // = select_solve_col(..).lds
-void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride);
-int64_t col_dual_doubles(const KParams &P, int m);                // column kernel: doubles of one instance's slack / dual block (at oDUAL)
+void lds_workspace_fill(KParams *P, int m);                       // the LDS-resident kernels' workspace: oPACK, oKT, oDUAL, oCKPT, oELAS and stride2 from WsLayout (nmpc_solve_common.h); m not supported: all 0
 hipError_t launch_eval(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, double *f, double *g, hipStream_t st, bool ofield = false);      // ofield: P.ofield is the obstacle field
 // KKT residuals of (w, lam_g, lam_x): res [B][6] = (stat, eq, ineq, bnd, compl, sign), grad_lag [B][nvar] or nullptr (include/nmpc.h, nmpc_kkt_batch)
 hipError_t launch_kkt(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,

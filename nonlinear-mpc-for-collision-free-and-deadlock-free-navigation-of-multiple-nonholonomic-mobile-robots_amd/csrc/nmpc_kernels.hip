@@ -151,14 +151,15 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
     double *base = ws + inst * P.stride;
     double *X = base + P.oX, *U = base + P.oU, *LAM = base + P.oLAM, *S = base + P.oS, *Z = base + P.oZ;
     double *DX = base + P.oDX, *DU = base + P.oDU, *LAMN = base + P.oLAMN, *DS = base + P.oDS, *DZ = base + P.oDZ;
-    double *EL = base + P.oEL, *DEL = EL + (size_t)(P.N + 1) * P.nh;      // elastic variables t and their steps (elastic phase only; pair / obstacle slots)
+    double *EL = base + P.oEL, *DEL = EL + HbmWs::el_half(P.N, P.nh);      // elastic variables t and their steps (elastic phase only; pair / obstacle slots)
     const double rho = P.rho_el;
     bool el = false;      // elastic phase: the second restart of last resort (oracle/nmpc_oracle.c has the derivation)
 #define ELSLOT(s) (el && (s) >= P.o_pr)
     double *SN = base + P.oSN, *CS = base + P.oCS, *Cd = base + P.oC, *H = base + P.oH, *GX = base + P.oGX;
     double *HUU = base + P.oHUU, *GU = base + P.oGU, *HVT = base + P.oHVT, *HTT = base + P.oHTT;
     double *KG = base + P.oKG, *KFF = base + P.oKFF;
-    double *CKP = base + P.oCKP;      // saved cost-to-go [P | p] of the backward sweep, one slot of NX * NX + NX doubles per NMPC_CKPT_EVERY stages
+    constexpr int CKS = HbmWs::ckpt_slot(NX);
+    double *CKP = base + P.oCKP;      // saved cost-to-go [P | p] of the backward sweep, one slot of CKS doubles per NMPC_CKPT_EVERY stages
 
     const double *pp = p_in + inst * (2 * NX);
     const double *wi = w0 + inst * (size_t)P.nvar;
@@ -418,14 +419,14 @@ __global__ __launch_bounds__(TPB) void solve_kernel(const KParams P, const doubl
                     sP[c * NX + c] += Z[N * NH + P.o_xl + s] / S[N * NH + P.o_xl + s] + Z[N * NH + P.o_xu + s] / S[N * NH + P.o_xu + s];
                 }
             } else {
-                const double *ck = CKP + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * (NX * NX + NX);
+                const double *ck = CKP + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * CKS;
                 for (int e = tid; e < NX * NX; e += TPB) sP[e] = ck[e];
                 for (int c = tid; c < NX; c += TPB) sPv[c] = ck[NX * NX + c];
             }
             __syncthreads();
             for (int k = kst; k >= 0; k--) {
                 if (k < kst && (kst - k) % NMPC_CKPT_EVERY == 0) {      // save [P | p] entering this stage (each thread reads back its own words)
-                    double *ck = CKP + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * (NX * NX + NX);
+                    double *ck = CKP + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * CKS;
                     for (int e = tid; e < NX * NX; e += TPB) ck[e] = sP[e];
                     for (int c = tid; c < NX; c += TPB) ck[NX * NX + c] = sPv[c];
                 }

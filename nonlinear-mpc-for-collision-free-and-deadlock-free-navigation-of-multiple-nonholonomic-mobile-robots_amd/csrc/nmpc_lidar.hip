@@ -23,12 +23,21 @@
 #include <string.h>
 
 #include <type_traits>
+// Divisions of the stage-parallel phases: qdiv of nmpc_wave.h, under this kernel's own switch — NMPC_LIDAR_FAST_DIV=0 restores the IEEE
+// divisions here (A/B), whatever NMPC_FAST_DIV says for the swarm kernels
+#ifndef NMPC_LIDAR_FAST_DIV
+#define NMPC_LIDAR_FAST_DIV 1
+#endif
+#undef NMPC_FAST_DIV
+#define NMPC_FAST_DIV NMPC_LIDAR_FAST_DIV
+#include "nmpc_wave.h"     // reciprocals, qdiv, LogSum, wave-uniform values and the reductions of one wavefront, shared with the swarm kernels
 #include "nmpc_ipm.h"      // the controller of the interior-point iteration, shared with the swarm kernels (and through it include/nmpc_constants.h)
 #include "../../include/nmpc_lidar.h"
 #include "../../include/nmpc_debug.h"
 
 namespace nmpc_lidar {
 namespace ipm = nmpc::ipm;
+using nmpc::LogSum; using nmpc::qdiv; using nmpc::rcp2; using nmpc::uniform_f64; using nmpc::wsum; using nmpc::wmax; using nmpc::wave_min; using nmpc::wave_logsum;
 
 struct LParams {
     int32_t N, Nc, R, ns, max_iter, nvar, ng, np, n_ineq;      // n_ineq: finite bounds of the free variables (stages 1..N and the controls)
@@ -55,46 +64,6 @@ __device__ __forceinline__ double push_in(double v, double lo, double hi)
     return v;
 }
 
-// sum of log(s_i), s_i > 0, accumulated as (product of the mantissas, sum of the exponents): four instructions per term instead of a log
-// (~90, a fifth of the two phases that need the barrier function), one log per wavefront at the end.  The mantissa product is renormalised
-// after every term; a term <= 0 or NaN makes the result NaN like the log would.
-struct LogSum {
-    double m = 1.0, lo = INFINITY;
-    int e = 0;
-    __device__ __forceinline__ void add(double s_)
-    {
-        const double t = m * __builtin_amdgcn_frexp_mant(s_);
-        e += __builtin_amdgcn_frexp_exp(s_) + __builtin_amdgcn_frexp_exp(t);
-        m = __builtin_amdgcn_frexp_mant(t);
-        lo = fmin(lo, s_);
-    }
-};
-
-// reciprocal: v_rcp_f64 seed + two Newton steps (full fp64 accuracy; five dependent operations where the IEEE division chain has eleven — the
-// Riccati stage of a lone wavefront is one long dependency chain with two pivots in it)
-__device__ __forceinline__ double rcp_nr(double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-
-// Divisions of the stage-parallel phases: v_rcp_f64 + one Newton step and a multiply instead of the IEEE division chain (round 4; as qdiv of
-// nmpc_solve_common.h: <= 2.3e-15 relative, tools/rcp_probe.hip).  NMPC_LIDAR_FAST_DIV=0 restores the divisions (A/B).
-#ifndef NMPC_LIDAR_FAST_DIV
-#define NMPC_LIDAR_FAST_DIV 1
-#endif
-__device__ __forceinline__ double qdiv(double a, double b)
-{
-#if NMPC_LIDAR_FAST_DIV
-    double r = __builtin_amdgcn_rcp(b);
-    return a * fma(fma(-b, r, 1.0), r, r);
-#else
-    return a / b;
-#endif
-}
-
 #ifndef NMPC_LIDAR_DPP
 #define NMPC_LIDAR_DPP 1        // 1: column-per-lane Riccati stage (DPP broadcasts); 0: every lane walks the upper triangle (A/B)
 #endif
@@ -108,26 +77,6 @@ template <int L_> __device__ __forceinline__ void dpp_fmac(double &acc, double n
 template <int L_> __device__ __forceinline__ void dpp_fmac2(double &acc, double u, double nr)      // acc += u[lane L_ of my row] * nr
 {
     asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(u), "v"(nr), "n"(L_));
-}
-
-// wave reductions whose result the compiler knows to be uniform (scalar control flow)
-__device__ __forceinline__ double uni(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-__device__ __forceinline__ double wsum_(double v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return uni(v); }
-__device__ __forceinline__ double wmax_(double v) { for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o)); return uni(v); }
-__device__ __forceinline__ double wmin_(double v) { for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o)); return uni(v); }
-__device__ __forceinline__ double wlogsum_(LogSum a)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = a.m * __shfl_xor(a.m, o);
-        a.e += __shfl_xor(a.e, o) + __builtin_amdgcn_frexp_exp(t);
-        a.m = __builtin_amdgcn_frexp_mant(t);
-        a.lo = fmin(a.lo, __shfl_xor(a.lo, o));
-    }
-    const double r = fma((double)a.e, 0.693147180559945309417, log(a.m));
-    return uni((a.lo > 0.0) ? r : NAN);
 }
 
 // One wavefront per instance.  Data layout: every per-stage array of the instance's workspace is COMPONENT-MAJOR ([component][stage]),
@@ -169,6 +118,15 @@ __device__ __forceinline__ double wlogsum_(LogSum a)
 #ifndef NMPC_LIDAR_SADDR
 #define NMPC_LIDAR_SADDR 1
 #endif
+// Where one instance keeps the per-stage operands of the horizon recursions in LDS, in doubles from the start of dynamic LDS (the closed form:
+// include/nmpc_lidar.h).  The kernel carves by it and nmpc_lidar_create sizes the launch from it.
+struct LidarLds {
+    size_t SB, SC, SD, SP, SF, total;      // [N+1][13] [Nc][16] [N+1][3] [NMPC_LIDAR_MAX_RAYS][2] [N][12]
+    __host__ __device__ LidarLds(int N, int Nc)
+    {
+        SB = 0; SC = SB + (size_t)(N + 1) * 13; SD = SC + (size_t)Nc * 16; SP = SD + (size_t)(N + 1) * 3; SF = SP + 2 * NMPC_LIDAR_MAX_RAYS; total = SF + (size_t)N * 12;
+    }
+};
 template <class T> struct UPtr {
     T *b;
     __device__ __forceinline__ T &operator[](int i) const
@@ -198,11 +156,12 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
     const double T = P.T;
     const UPtr<double> wsb{ws + (size_t)b * (size_t)P.total};
     extern __shared__ double lsm[];
-    double *SB = lsm;                              // [N+1][13]  Hxx(4) gx(3) hvt sin cos pose(3)
-    double *SC = SB + (size_t)NP1 * 13;            // [Nc][16]   u(2) huu(2) gu(2) K(6) kff(2) du(2)
-    double *SD = SC + (size_t)Nc * 16;             // [N+1][3]   pose step; the adjoint recursion overwrites it with lambda+
-    double *SP = SD + (size_t)NP1 * 3;             // [R][2]     lidar points of stage 0 (16 ray slots)
-    double *SF = SP + 2 * NMPC_LIDAR_MAX_RAYS;     // [N][12]    stage maps of the forward recursion, then the stage terms of the adjoint one
+    const LidarLds L(N, Nc);
+    double *SB = lsm + L.SB;                       // [N+1][13]  Hxx(4) gx(3) hvt sin cos pose(3)
+    double *SC = lsm + L.SC;                       // [Nc][16]   u(2) huu(2) gu(2) K(6) kff(2) du(2)
+    double *SD = lsm + L.SD;                       // [N+1][3]   pose step; the adjoint recursion overwrites it with lambda+
+    double *SP = lsm + L.SP;                       // [R][2]     lidar points of stage 0 (16 ray slots)
+    double *SF = lsm + L.SF;                       // [N][12]    stage maps of the forward recursion, then the stage terms of the adjoint one
     const double *pp = p_in + (size_t)b * P.np, *wi = w0 + (size_t)b * P.nvar;
     double *wo = w_out + (size_t)b * P.nvar;
     const UPtr<const double> lbS{P.lb}, ubS{P.ub}, lbu{P.lb + (size_t)NP1 * ns}, ubu{P.ub + (size_t)NP1 * ns};      // component-major, stage 0 = -+inf
@@ -239,7 +198,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
     {   // the pinned stage-0 variables must respect their own bounds
         double bad = 0.0;
         for (int c = lane; c < ns; c += 64) { double v = (c < 3) ? pp[c] : pp[6 + (c - 3)]; if (v < P.lb0[c] || v > P.ub0[c]) bad = 1.0; }
-        if (wmax_(bad) > 0.0) {
+        if (wmax(bad) > 0.0) {
             for (int k = lane; k <= N; k += 64) for (int c = 0; c < ns; c++) wo[(size_t)k * ns + c] = SV(oV, k, c);
             for (int e = lane; e < 2 * Nc; e += 64) wo[(size_t)NP1 * ns + e] = wsb[oU + e];
             if (lane == 0) {
@@ -281,8 +240,8 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                     t_ += fabs(e); e_ = fmax(e_, fabs(e));
                 }
         }
-        th = wsum_(t_); ec = wmax_(e_);
-        return wsum_(f);
+        th = wsum(t_); ec = wmax(e_);
+        return wsum(f);
     };
 
     double mu = P.mu_init, f = 0.0, th0 = 0.0, e_c = 0.0;
@@ -399,11 +358,11 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                     if (k < Nc - 1) ctrl_rows(j, g0, g1); else { pu0 += g0; pu1 += g1; }
                 }
             }
-            pu0 = wsum_(pu0); pu1 = wsum_(pu1);
+            pu0 = wsum(pu0); pu1 = wsum(pu1);
             if (lane == 0) ctrl_rows(Nc - 1, pu0, pu1);       // the held control: the sum over its stages
-            e_d = wmax_(e_d); e_h = wmax_(e_h); zsum = wsum_(zsum); lsum = wsum_(lsum); cmax = wmax_(cmax); cmin = wmin_(cmin);
+            e_d = wmax(e_d); e_h = wmax(e_h); zsum = wsum(zsum); lsum = wsum(lsum); cmax = wmax(cmax); cmin = wave_min(cmin);
             const ipm::OptErr oe = ipm::opt_error(e_d, e_c, e_h, lsum, zsum, cmax, (double)(N * ns + n_ineq), (double)(n_ineq > 0 ? n_ineq : 1));
-            const double s_d = oe.s_d, s_c = oe.s_c, E0 = uni(oe.E0);
+            const double s_d = oe.s_d, s_c = oe.s_c, E0 = uniform_f64(oe.E0);
             kkt = E0;
             if (!(E0 == E0)) { if (ipm::cold_retry_left(lad) && it < P.max_iter) { cold_retry(); break; } status = NMPC_STATUS_NUMERIC; break; }
             if (E0 <= P.tol) { status = NMPC_STATUS_CONVERGED; break; }
@@ -411,8 +370,8 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             if (ipm::cold_retry_due(lad, it)) { cold_retry(); break; }
             // wave-uniform values that live across phases go back to scalar registers (arithmetic on them runs on the vector ALU and would
             // leave them in vector registers — the ones the allocator then spills to scratch and reloads inside the hot loops)
-            mu = uni(ipm::barrier_update(mu, P.tol, e_d / s_d, e_c, e_h, cmax, cmin, s_c));
-            const double tau = uni(ipm::frac_to_boundary(mu));
+            mu = uniform_f64(ipm::barrier_update(mu, P.tol, e_d / s_d, e_c, e_h, cmax, cmin, s_c));
+            const double tau = uniform_f64(ipm::frac_to_boundary(mu));
             LP(1);
 
             // ---- B0. condensed stage blocks, one stage per lane, straight into LDS.  slot: v = mu/s - sigma (h - s), sigma = z/s
@@ -491,7 +450,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             __syncthreads();
             LP(2);
             // ---- B. Riccati sweep on z = (pose (3), held control (2)) with inertia correction; uniform on all lanes, stage in registers
-            double delta = uni(ipm::shift_first(need_shift, delta_last));
+            double delta = uniform_f64(ipm::shift_first(need_shift, delta_last));
             int ntry = 0;
             bool ok;
             for (;;) {
@@ -552,12 +511,12 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                         m4 = fma(huu1 + delta, i4_, fma(gu1, i5_, m4));
                         const double dv = lane_val(m3, 3), d1o = lane_val(m4, 4);
                         if (!(dv > 0.0)) return false;
-                        const double rdv = rcp_nr(dv);
+                        const double rdv = rcp2(dv);
                         const double t3 = m3 * rdv, nt3 = -t3;        // pivot row 3 / pivot, per column
                         dpp_fmac<3>(m0, nt3); dpp_fmac<3>(m1, nt3); dpp_fmac<3>(m2, nt3); dpp_fmac<3>(m4, nt3);
                         const double d1 = lane_val(m4, 4);
                         if (!(d1 > 1e-9 * fabs(d1o)) || !(d1 > 0.0)) return false;
-                        const double rd1 = rcp_nr(d1);
+                        const double rd1 = rcp2(d1);
                         const double t4 = m4 * rd1, nt4 = -t4;
                         dpp_fmac<4>(m0, nt4); dpp_fmac<4>(m1, nt4); dpp_fmac<4>(m2, nt4);
                         // gains [K | kff] (columns 0..2 | column 5): second control -t4, first -(t3 - (M34 / d3) t4), M34 / d3 = t3 of column 4
@@ -615,10 +574,10 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                         M33 += huu0 + delta; M44 += huu1 + delta;
                         mv3 += gu0; mv4 += gu1;
                         const double dv = M33;
-                        if (!(uni(dv) > 0.0)) return false;
+                        if (!(uniform_f64(dv) > 0.0)) return false;
                         const double rdv = 1.0 / dv;          // two reciprocals per stage (the recursion is uniform: every lane pays them)
                         const double l43 = M34 * rdv, d1o = M44, d1 = d1o - l43 * M34;
-                        if (!(uni(d1) > 1e-9 * fabs(uni(d1o))) || !(uni(d1) > 0.0)) return false;
+                        if (!(uniform_f64(d1) > 1e-9 * fabs(uniform_f64(d1o))) || !(uniform_f64(d1) > 0.0)) return false;
                         const double rd1 = 1.0 / d1;
                         // gains: [K | kff] = -[[M33 M34], [M34 M44]]^-1 [M3q M4q | mv3 mv4], q = x, y, theta
                         const double r3[4] = {M03, M13, M23, mv3}, r4[4] = {M04, M14, M24, mv4};
@@ -652,7 +611,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
 #endif
                 if (ok) break;
                 ntry++;
-                delta = uni(ipm::shift_next(delta, delta_last));      // the whole sweep is repeated
+                delta = uniform_f64(ipm::shift_next(delta, delta_last));      // the whole sweep is repeated
                 if (ipm::shift_exhausted(delta)) break;
             }
             if (!ok) { if (ipm::cold_retry_left(lad)) { cold_retry(); it++; break; } status = NMPC_STATUS_NUMERIC; break; }
@@ -806,7 +765,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                             if (k0 - i >= 1) { SD[3 * (k0 - i)] = l_[i][0]; SD[3 * (k0 - i) + 1] = l_[i][1]; SD[3 * (k0 - i) + 2] = l_[i][2]; }
                     }
                 }
-                mult_max = wmax_(mult_max);
+                mult_max = wmax(mult_max);
             }
             __syncthreads();
             LP(6);
@@ -842,15 +801,15 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                 const int j = o >> 1, cnt = (j < Nc - 1) ? 1 : N - Nc + 1;
                 dphi += cnt * 2 * P.r[o & 1] * u * du;
             }
-            a_p = wmin_(a_p); a_d = wmin_(a_d); dphi = wsum_(dphi); thh = wsum_(thh);
-            const double lgs = wlogsum_(lgs_);
+            a_p = wave_min(a_p); a_d = wave_min(a_d); dphi = wsum(dphi); thh = wsum(thh);
+            const double lgs = wave_logsum(lgs_);
             LP(7);
             // ---- E. l1 merit backtracking (non-monotone reference: max of the last merit values of this barrier problem)
-            const double theta0 = uni(th0 + thh), phi0 = uni(f - mu * lgs);
-            if (theta0 > 0.0) nu_pen = uni(ipm::penalty_update(nu_pen, dphi, theta0, mult_max));
-            const double Dm = uni(dphi - nu_pen * theta0);
+            const double theta0 = uniform_f64(th0 + thh), phi0 = uniform_f64(f - mu * lgs);
+            if (theta0 > 0.0) nu_pen = uniform_f64(ipm::penalty_update(nu_pen, dphi, theta0, mult_max));
+            const double Dm = uniform_f64(dphi - nu_pen * theta0);
             double alpha = a_p, ft = f, tht = th0, ect = e_c;
-            const double mref = uni(mref_h.reference(mu, nu_pen, uni(phi0 + nu_pen * theta0)));
+            const double mref = uniform_f64(mref_h.reference(mu, nu_pen, uniform_f64(phi0 + nu_pen * theta0)));
             const bool wd_fire = ipm::watchdog_fires(n_short, a_p);
             bool wd_took = false;
             for (int ls = 0; ls < 30; ls++) {
@@ -880,15 +839,15 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
                 }
                 __syncthreads();
                 ft = eval_point(oVt, oUt, tht, ect);
-                const double lgt = wlogsum_(lgt_);
-                tb = wsum_(tb);
+                const double lgt = wave_logsum(lgt_);
+                tb = wsum(tb);
                 const double mt = (ft - mu * lgt) + nu_pen * (tht + tb);
                 if (wd_fire && isfinite(mt)) { mref_h.reset(); wd_took = true; break; }      // watchdog: the fraction-to-the-boundary step without the merit test
                 if (ipm::armijo(mt, mref, alpha, Dm, phi0)) break;
-                if (ls < 29) alpha = uni(alpha * 0.5);
+                if (ls < 29) alpha = uniform_f64(alpha * 0.5);
                 __syncthreads();
             }
-            a_d = uni(fmin(a_d, alpha));
+            a_d = uniform_f64(fmin(a_d, alpha));
             LP(8);
             ipm::count_step(lad, alpha);
             n_short = ipm::watchdog_count(n_short, wd_took, alpha, a_p);
@@ -943,7 +902,7 @@ __global__ __launch_bounds__(64, W_) void lidar_solve_kernel(const LParams P, in
             it++;
             if (ipm::stalled(lad)) {
                 if (ipm::restarts_used_up(lad)) { if (ipm::cold_retry_left(lad)) { cold_retry(); break; } status = NMPC_STATUS_STALLED; break; }
-                ipm::barrier_restart_begin(lad); mu = uni(ipm::restart_mu(mu, P.mu_init)); restarting = true;
+                ipm::barrier_restart_begin(lad); mu = uniform_f64(ipm::restart_mu(mu, P.mu_init)); restarting = true;
                 break;
             }
         }
@@ -1091,8 +1050,8 @@ int32_t nmpc_lidar_create(const nmpc_lidar_config_t *cfg, const double *lbx, con
     if (hipGetDevice(&h->device) != hipSuccess) { free(h); return NMPC_E_HIP; }
     { hipDeviceProp_t prop; h->n_cu = (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256; }
     h->cfg = *cfg; h->max_batch = max_batch;
-    h->lds_bytes = sizeof(double) * ((size_t)(N + 1) * 13 + (size_t)Nc * 16 + (size_t)(N + 1) * 3 + 2 * NMPC_LIDAR_MAX_RAYS + (size_t)N * 12);
-    if (h->lds_bytes > 160 * 1024) { free(h); return NMPC_E_ARG; }       // horizon beyond the LDS of a CU: 8 (16 (N + 1) + 16 Nc + 12 N + 32) bytes <= 160 KB, i.e. N <= ~560 with Nc = N / 2
+    h->lds_bytes = sizeof(double) * nmpc_lidar::LidarLds(N, Nc).total;
+    if (h->lds_bytes > 160 * 1024) { free(h); return NMPC_E_ARG; }       // horizon beyond the LDS of a CU: N <= ~560 with Nc = N / 2 (include/nmpc_lidar.h)
     nmpc_lidar::LParams &P = h->P;
     memset(&P, 0, sizeof(P));
     P.N = N; P.Nc = Nc; P.R = R; P.ns = ns; P.max_iter = cfg->max_iter; P.nvar = nv; P.ng = nmpc_lidar_n_g(cfg); P.np = nmpc_lidar_n_p(cfg);

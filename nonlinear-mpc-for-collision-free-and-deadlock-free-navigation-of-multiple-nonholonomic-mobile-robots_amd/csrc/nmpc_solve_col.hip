@@ -129,13 +129,15 @@ template <int M_, int THB> struct GC : G2<M_, THB> {
 // Where one instance keeps its arrays, in doubles.  First the block every instantiation has in LDS, from the start of dynamic LDS: what the
 // serial sweeps touch (states, controls, multipliers, trig cache, step) plus one scratch region.  Then the block of the slacks and duals of the
 // inequality rows, which only the stage-parallel phases visit: it follows the first block in LDS, or starts at KParams::oDUAL in the
-// instance's workspace (see the kernel).  The kernel, its multiplier epilogue, the poison fill of debug builds, col_lds_bytes and the
-// workspace carve-up (col_dual_doubles) all take the layout from here.
+// instance's workspace (see the kernel).  Behind the blocks held in LDS, by the data layout dl = DL & 3 of the instantiation: the stage
+// factors (dl >= 2) and the stage packs (dl >= 3), which otherwise live in the workspace too.  The kernel, its multiplier epilogue, the
+// poison fill of debug builds, col_lds_bytes and the workspace layout (lds_workspace_fill) all take the layout from here.
 template <int M_, int THB> struct ColLayout {
     using G = G2<M_, THB>;
     static constexpr int RG = G::KTS > G::PACK ? G::KTS : G::PACK;      // least size of the scratch region: a staged stage factor or pack (sized, like the workspace, for G2's pack)
     int X, U, LAM, SN, CS, DX, DU, RV, XS, RED, end;                    // [N1*NX] [N*NU] [N1*NX] [N*M] [N*M] [N1*NX] [N*NU] [max(N1*NX, RG)] [NX] [8]
     int SPp, ZPp, SO, ZO, ZUL, ZUU, ZXL, ZXU, SUL, SUU, dual;           // [N1*NP] x 2, [N1*MK] x 2, [N*NU] x 2, [N1*NXB] x 2, [N*NU] x 2; dual: the block's length
+    int nkt, npk;                                                       // [N][KTS] stage factors, [N + 1][GC::PACK] stage packs (the terminal pack last: the whole-slice staging of pack N - 1 may read into it)
     __host__ __device__ ColLayout(int N, int K)
     {
         const int N1 = N + 1, MK = M_ * K;
@@ -143,7 +145,12 @@ template <int M_, int THB> struct ColLayout {
         XS = RV + ((N1 * G::NX > RG) ? N1 * G::NX : RG); RED = XS + G::NX; end = RED + 8;
         SPp = 0; ZPp = SPp + N1 * G::NP; SO = ZPp + N1 * G::NP; ZO = SO + N1 * MK; ZUL = ZO + N1 * MK; ZUU = ZUL + N * G::NU; ZXL = ZUU + N * G::NU;
         ZXU = ZXL + N1 * G::NXB; SUL = ZXU + N1 * G::NXB; SUU = SUL + N * G::NU; dual = SUU + N * G::NU;
+        nkt = N * G::KTS; npk = (N + WsLayout<M_, THB>::PACKS_BEYOND) * GC<M_, THB>::PACK;
     }
+    // LDS of data layout dl: where the stage factors (dl >= 2) and the stage packs (dl >= 3) start, and the doubles of the whole
+    template <class T> __host__ __device__ T kt(T base, int dl) const { return base + end + (dl ? dual : 0); }
+    template <class T> __host__ __device__ T pack(T base, int dl) const { return kt(base, dl) + nkt; }
+    __host__ __device__ int total(int dl) const { return kt(0, dl) + (dl >= 2 ? nkt : 0) + (dl >= 3 ? npk : 0); }
 };
 
 // TPBK: threads per instance.  64 = the throughput shape (one wavefront per instance).  128 (256) = the LATENCY shape: a second wavefront (three more) shares
@@ -160,6 +167,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                                                         double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
 {
     using G = GC<M_, THB>;
+    using W = WsLayout<M_, THB>;
     constexpr int TPB = TPBK;
     static_assert(TPBK == 64 || TPBK == 128 || TPBK == 256, "one, two or four wavefronts per instance");
     constexpr int DLL = DL & 3;            // data layout (the obstacle source bit apart)
@@ -219,13 +227,12 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 
     // DL >= 2 (small teams, throughput shape): the stage factors — written by the backward sweep, read by the forward sweep — live in LDS as well, DL >= 3:
     // the stage packs too; otherwise both are in the instance's workspace (HBM/L2)
-    double *const dl_end = sm + L.end + (DLL ? L.dual : 0);
-    double *gkt = (DLL >= 2) ? dl_end : ws + inst * P.stride2 + P.oKT;       // [N][KTS]
-    double *gpack = (DLL >= 3) ? dl_end + (size_t)N * G::KTS : ws + inst * P.stride2 + P.oPACK;   // [N][PACK] + terminal [2*NX]
+    double *gkt = (DLL >= 2) ? L.kt(sm, DLL) : ws + inst * P.stride2 + P.oKT;       // [N][KTS]
+    double *gpack = (DLL >= 3) ? L.pack(sm, DLL) : ws + inst * P.stride2 + P.oPACK;   // [N][PACK] + terminal [2*NX]
     const UArr TPp{ws + inst * P.stride2 + P.oELAS, 0};           // [N1*NP]   elastic variables of the pair rows (elastic phase only; always in the workspace)
-    const UArr TOb{ws + inst * P.stride2 + P.oELAS, N1 * NP};     // [N1*MK]   ... of the obstacle rows
+    const UArr TOb{ws + inst * P.stride2 + P.oELAS, W::el_pair(N1)};     // [N1*MK]   ... of the obstacle rows
     const double rho = P.rho_el;
-    double *gck = ws + inst * P.stride2 + P.oCKPT;     // [(N-1)/NMPC_CKPT_EVERY + 1][NX + 1][64]  saved cost-to-go of the backward sweep (column-per-lane registers as they are)
+    double *gck = ws + inst * P.stride2 + P.oCKPT;     // [W::ckpt_slots(N)][NX + 1][64]  saved cost-to-go of the backward sweep (column-per-lane registers as they are)
     const double *pp = p_in + inst * (2 * NX);
     const double *wi = w0 + inst * (size_t)P.nvar;
     double *wo = w_out + inst * (size_t)P.nvar;
@@ -233,8 +240,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 #ifdef NMPC_POISON
     {   // debug build: every LDS word and the instance's HBM workspace start as NMPC_POISON, so that a read of anything this solve did not
         // write shows up as a parity failure instead of depending on what ran on the CU before
-        const int nl = L.end + (DLL ? L.dual : 0) + (DLL >= 2 ? N * G::KTS : 0) + (DLL >= 3 ? N1 * G::PACK : 0);
-        for (int e = tid; e < nl; e += TPB) sm[e] = NMPC_POISON;
+        for (int e = tid; e < L.total(DLL); e += TPB) sm[e] = NMPC_POISON;
         for (size_t e = tid; e < (size_t)P.stride2; e += TPB) ws[inst * P.stride2 + e] = NMPC_POISON;
         __syncthreads();
     }
@@ -841,11 +847,11 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 static_for<NC, RR>([&](auto rc) { constexpr int r = decltype(rc)::value; m[r] = (c_state && rw == rh && rn == r) ? hdN : 0.0; });
                 m[RR] = gN;
             } else {
-                const double *ck = gck + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * ((NX + 1) * 64) + tid;
+                const double *ck = gck + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * W::CKPT_SLOT + tid;
                 static_for<0, NS + 1>([&](auto rc) { constexpr int r = decltype(rc)::value; const double v = ck[r * 64]; m[NC + r] = cvalid ? v : 0.0; });
             }
             constexpr int PKR = (G::PACK + TPB - 1) / TPB;
-            constexpr bool FULL = PKR * TPB <= RG0 && PKR * TPB <= 2 * G::PACK;
+            constexpr bool FULL = PKR * TPB <= RG0 && PKR * TPB <= (1 + W::PACKS_BEYOND) * G::PACK;      // (see the other sweep)
             double pkr[PKR];
 #pragma unroll
             for (int t = 0; t < PKR; t++) { int e = tid + t * TPB; pkr[t] = (FULL || e < G::PACK) ? gpack[(size_t)kst * G::PACK + e] : 0.0; }
@@ -881,7 +887,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 }
                 if (ckc == NMPC_CKPT_EVERY) {      // save the cost-to-go entering this stage: state rows and right-hand side as the lanes hold them
                     ckc = 0;
-                    double *ck = gck + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * ((NX + 1) * 64) + tid;
+                    double *ck = gck + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * W::CKPT_SLOT + tid;
                     if (cvalid) static_for<0, NS + 1>([&](auto rc) { constexpr int r = decltype(rc)::value; ck[r * 64] = m[NC + r]; });
                 }
                 ckc++;
@@ -1028,14 +1034,14 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 static_for<0, NX>([&](auto rc) { constexpr int r = decltype(rc)::value; m[NU + r] = (is_state && ms == r) ? hdN : 0.0; });
                 m[NZ] = gN;
             } else {
-                const double *ck = gck + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * ((NX + 1) * 64) + tid;
+                const double *ck = gck + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * W::CKPT_SLOT + tid;
                 static_for<0, NX + 1>([&](auto rc) { constexpr int r = decltype(rc)::value; const double v = ck[r * 64]; m[NU + r] = is_state ? v : 0.0; });
             }
             // prefetch pack N-1 into registers
+            // whole 64-lane slices where they fit the scratch region: the tail of the last slice reads into the next pack, which exists for every
+            // stage (the layouts hold PACKS_BEYOND more packs than stages): no exec-masked tail in every stage.  Measured +3.3 %
             constexpr int PKR = (G::PACK + TPB - 1) / TPB;
-            // whole 64-lane slices where they fit the scratch region (the tail of the last slice reads into the next pack / the terminal
-            // block, in bounds: (N+1) packs are allocated and PKR*64 <= 2*PACK): no exec-masked tail in every stage.  Measured +3.3 %
-            constexpr bool FULL = PKR * TPB <= RG0 && PKR * TPB <= 2 * G::PACK;
+            constexpr bool FULL = PKR * TPB <= RG0 && PKR * TPB <= (1 + W::PACKS_BEYOND) * G::PACK;
             double pkr[PKR];
 #pragma unroll
             for (int t = 0; t < PKR; t++) { int e = tid + t * TPB; pkr[t] = (FULL || e < G::PACK) ? gpack[(size_t)kst * G::PACK + e] : 0.0; }
@@ -1067,7 +1073,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 }
                 if (ckc == NMPC_CKPT_EVERY) {      // save the cost-to-go entering this stage (state lanes: rows NU.. and the right-hand side)
                     ckc = 0;
-                    double *ck = gck + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * ((NX + 1) * 64) + tid;
+                    double *ck = gck + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * W::CKPT_SLOT + tid;
                     if (is_state) static_for<0, NX + 1>([&](auto rc) { constexpr int r = decltype(rc)::value; ck[r * 64] = m[NU + r]; });
                 }
                 ckc++;
@@ -1669,12 +1675,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
 // LDS bytes of one instance of the column-per-lane kernel
 template <int M_, int THB> static size_t col_lds_bytes(const KParams &P, bool duals, int fl = 0)      // fl: 2 = + stage factors, 3 = + stage packs (see the kernel)
 {
-    const ColLayout<M_, THB> L(P.N, P.K);
-    size_t d = L.end;
-    if (duals) d += L.dual;
-    if (duals && fl >= 2) d += (size_t)P.N * G2<M_, THB>::KTS;
-    if (duals && fl >= 3) d += (size_t)(P.N + 1) * GC<M_, THB>::PACK;
-    return d * sizeof(double);
+    return (size_t)ColLayout<M_, THB>(P.N, P.K).total(duals ? (fl >= 2 ? fl : 1) : 0) * sizeof(double);
 }
 // slacks / duals in LDS: up to four robots, when eight instances still share a CU
 #ifndef NMPC_COL_DL_MAXM
@@ -1803,10 +1804,16 @@ size_t col_kernel_bytes(const KParams &P, int m, int shape)
     return select_solve_col(P, m, shape, false, &v) ? v.lds : 0;
 }
 
-// doubles of the slack / dual block of one instance (ColLayout): what the workspace carve-up reserves at KParams::oDUAL (0 if m is not supported)
-int64_t col_dual_doubles(const KParams &P, int m)
+// the workspace of one instance of the LDS-resident kernels (WsLayout, with this kernel's slack / dual block) as KParams carries it
+template <int M_, int THB> static void ws_fill(KParams *P)
 {
-    return for_team_size(m, (int64_t)0, [&](auto M) { return (int64_t)(P.thb ? ColLayout<decltype(M)::value, 1>(P.N, P.K).dual : ColLayout<decltype(M)::value, 0>(P.N, P.K).dual); });
+    const WsLayout<M_, THB> w(P->N, P->K, ColLayout<M_, THB>(P->N, P->K).dual);
+    P->oPACK = w.PACK; P->oKT = w.KT; P->oDUAL = w.DUAL; P->oCKPT = w.CKPT; P->oELAS = w.ELAS; P->stride2 = w.total;
+}
+void lds_workspace_fill(KParams *P, int m)
+{
+    P->oPACK = P->oKT = P->oDUAL = P->oCKPT = P->oELAS = P->stride2 = 0;
+    for_team_size(m, 0, [&](auto M) { return P->thb ? ws_fill<decltype(M)::value, 1>(P) : ws_fill<decltype(M)::value, 0>(P), 0; });
 }
 #endif      // entry points
 

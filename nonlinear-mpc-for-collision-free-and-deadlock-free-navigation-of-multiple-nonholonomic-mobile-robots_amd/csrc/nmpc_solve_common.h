@@ -1,9 +1,12 @@
-// nmpc_solve_common.h — geometry, wave primitives and the start / restart / exit text shared by the three swarm solve kernels (nmpc_kernels.hip:
-// HBM-resident; nmpc_solve_lds.hip: element-per-lane Riccati stage; nmpc_solve_col.hip: column-per-lane, register-resident Riccati stage), and
-// the pinned-order arithmetic helpers of the two LDS-resident ones.  The scalar controller of the iteration is nmpc_ipm.h.
-// NOT shared, on purpose: kernel 1 keeps its own constraint arithmetic (slot_h, slot_jd, jxT_robot and its stage-0 pre-check in nmpc_kernels.hip),
-// which rounds differently from the fma-pinned h_pair / h_obs below — unifying it would move kernel 1's results; init_barrier, merit, the
-// stage-parallel phases and the sweeps belong to each kernel's data layout and stay there.
+// nmpc_solve_common.h — what the three swarm solve kernels share (nmpc_kernels.hip: HBM-resident; nmpc_solve_lds.hip: element-per-lane Riccati
+// stage; nmpc_solve_col.hip: column-per-lane, register-resident Riccati stage): the obstacle field, the simple bounds, the start / restart /
+// exit text; and what the two LDS-resident ones share: the geometry of a stage (G2), the layout of their per-instance workspace (WsLayout: one
+// definition for create and for both kernels) and the pinned-order arithmetic helpers.  The scalar controller of the iteration is nmpc_ipm.h;
+// reciprocals, qdiv, LogSum, uniform_f64 and the reductions are nmpc_wave.h, which the LIDAR kernel includes as well.
+// NOT shared, on purpose: each kernel's LDS layout sits next to it (ColLayout, LdsLayout; kernel 1's workspace is carved up by fill_params,
+// HbmWs in nmpc_device.h naming its two structured arrays); kernel 1 keeps its own constraint arithmetic (slot_h, slot_jd, jxT_robot and its
+// stage-0 pre-check in nmpc_kernels.hip), which rounds differently from the fma-pinned h_pair / h_obs below — unifying it would move kernel 1's
+// results; init_barrier, merit, the stage-parallel phases and the sweeps belong to each kernel's data layout and stay there.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -13,6 +16,7 @@
 
 #include "nmpc_device.h"
 #include "nmpc_ipm.h"
+#include "nmpc_wave.h"
 
 namespace nmpc {
 
@@ -42,6 +46,35 @@ template <int M_, int THB> struct G2 {
     // even row stride LDC (16-byte aligned rows: the forward sweep loads its row with dwordx4)
     static constexpr int LDC = (NZ + 3) & ~1;
     static constexpr int KTS = ((NU * LD + NU > NU * LDC ? NU * LD + NU : NU * LDC) + 7) / 8 * 8;
+    // what the sweeps rely on: either kernel's rows fit the slot, and column NZ + 1 of a row of the column kernel — the padding slot its idle
+    // lanes store to, also one slot ahead (the deferred store of row NU - 1) — lies inside the row
+    static_assert(NU * LD + NU <= KTS && NU * LDC <= KTS && NZ + 1 < LDC, "a stage factor and its padding slots stay inside [KTS]");
+};
+
+// Where one instance of the two LDS-resident kernels keeps its arrays in the workspace, in doubles from the instance's base; every array
+// starts on a 128-byte boundary.  Create copies the offsets into KParams (lds_workspace_fill) and the kernels read them from there —
+// computing them in the kernel costs scalar registers the column kernel does not have; the sizes of a slot and of the two halves of the
+// elastic block the kernels take from here.
+template <int M_, int THB> struct WsLayout {
+    using G = G2<M_, THB>;
+    static constexpr int PACKS_BEYOND = 1;                     // packs behind the N stage packs: the terminal one ([2*NX] of it used)
+    static constexpr int CKPT_PP = G::NX * G::NX + G::NX;      // the element-per-lane kernel saves [P | p] in a slot,
+    static constexpr int CKPT_SLOT = (G::NX + 1) * 64;         // the column kernel its NX + 1 registers lane by lane: the slot's doubles
+    static_assert(CKPT_PP <= CKPT_SLOT, "[P | p] of the element-per-lane kernel fits a checkpoint slot");
+    static __host__ __device__ constexpr int ckpt_slots(int N) { return (N - 1) / NMPC_CKPT_EVERY + 1; }      // cost-to-go saved every NMPC_CKPT_EVERY stages of the backward sweep
+    static __host__ __device__ constexpr int el_pair(int N1) { return N1 * G::NP; }                          // elastic block: t of the pair rows [N1][NP] (N1 = N + 1),
+    static __host__ __device__ constexpr int el_obs(int N, int K) { return (N + 1) * M_ * K; }                // then of the obstacle rows [N1][M K]
+    // [N + 1][G::PACK] stage packs (the column kernel's are shorter, GC) | [N][KTS] stage factors | [dual] the column kernel's slacks and duals
+    // (ColLayout::dual) | [ckpt_slots][CKPT_SLOT] | [el_pair + el_obs] (elastic phase only)
+    int64_t PACK, KT, DUAL, CKPT, ELAS, total;
+    __host__ __device__ WsLayout(int N, int K, int dual)
+    {
+        int64_t o = 0;
+        auto take = [&](int64_t n) { const int64_t at = o; o += (n + 15) / 16 * 16; return at; };
+        PACK = take((int64_t)(N + PACKS_BEYOND) * G::PACK); KT = take((int64_t)N * G::KTS); DUAL = take(dual);
+        CKPT = take((int64_t)ckpt_slots(N) * CKPT_SLOT); ELAS = take((int64_t)el_pair(N + 1) + el_obs(N, K));
+        total = o;
+    }
 };
 
 // ---- the obstacle field: component c (0 ox, 1 oy, 2 r) of obstacle o as the obstacle rows of stage k (evaluated at X_k) of one instance see
@@ -70,27 +103,7 @@ template <int OS> struct ObsField {
 // iteration (Newton right-hand side, step-size rule, multiplier recursion, update).  With sigma = z/s up to 1e13 a
 // last-bit difference between two sites (e.g. a differently contracted a*b+c) shows up as 1e-7 in the dual residual, so
 // every site goes through these helpers, whose operation order is pinned with explicit fma().
-// Divisions of the stage-parallel phases (sigma = z / s, mu / s, dz, the step-length quotients): NMPC_FAST_DIV = 1 replaces the IEEE division
-// chain (~12 instructions: div_scale x2, rcp, four multiply-adds, div_fmas, div_fixup) by v_rcp_f64 + one Newton step and a multiply (4): relative
-// error <= 2.3e-15 against the division (tools/rcp_probe.hip).  Every site of one quantity goes through the same helper, so the sites stay
-// consistent with each other (see above).
-// A/B in one session (round 4): six robots B=4096 262 k -> 280 k solves/s, B=16384 388 k -> 410 k, a lone wave +10 %, mean iterations 29.0735 -> 29.0720.
-#ifndef NMPC_FAST_DIV
-#define NMPC_FAST_DIV 1
-#endif
-__device__ __forceinline__ double rcp1(double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-    return fma(fma(-d, r, 1.0), r, r);
-}
-__device__ __forceinline__ double qdiv(double a, double b)
-{
-#if NMPC_FAST_DIV
-    return a * rcp1(b);
-#else
-    return a / b;
-#endif
-}
+// Their divisions go through qdiv (nmpc_wave.h) for the same reason.
 __device__ __forceinline__ double h_pair(double ex, double ey, double dmin2) { return fma(ex, ex, ey * ey) - dmin2; }
 __device__ __forceinline__ double ds_pair(double ex, double ey, double ddx, double ddy, double dmin2, double sv)
 {
@@ -159,7 +172,7 @@ template <int TPB> __device__ __forceinline__ void lds_sync()
 // reciprocal of a pivot: v_rcp_f64 seed + Newton steps.  NMPC_RCP_STEPS = 1 (round 4): the seed is good to about single precision, one step
 // leaves ~1e-14 relative — the factorisation of an interior-point step does not need more (iteration counts of the bench batches equal to
 // 1e-5 relative, parity tests unchanged) and the two dependent multiply-adds it saves sit on the pivot chain of every stage: A/B in one
-// session, six robots B=4096 +2.3 %, B=16384 +1.2 %.  2 = full fp64 accuracy (rounds 2-3).
+// session, six robots B=4096 +2.3 %, B=16384 +1.2 %.  2 = full fp64 accuracy (rounds 2-3; rcp2 of nmpc_wave.h, which the LIDAR kernel always takes).
 #ifndef NMPC_RCP_STEPS
 #define NMPC_RCP_STEPS 1
 #endif
@@ -220,44 +233,6 @@ template <int M_> constexpr bool pair_of_ok()
 }
 static_assert(pair_of_ok<1>() && pair_of_ok<2>() && pair_of_ok<3>() && pair_of_ok<4>() && pair_of_ok<5>() && pair_of_ok<6>() && pair_of_ok<7>() &&
               pair_of_ok<8>() && pair_of_ok<9>() && pair_of_ok<10>(), "pair_of is the inverse of pidx");
-
-// A value every lane of the wave holds identically (a finished reduction, an LDS word read at a wave-uniform address),
-// moved through v_readfirstlane: the compiler then KNOWS it is wave-uniform, so the branches that depend on it (line-search
-// acceptance, convergence, pivot failure, barrier update) become scalar branches instead of exec-masked divergent regions.
-__device__ __forceinline__ double uniform_f64(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
-template <int TPB> __device__ __forceinline__ double wsum(double v, double *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if constexpr (TPB > 64) {
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double t = 0.0;
-        for (int w = 0; w < TPB / 64; w++) t += red[w];
-        v = t;
-    }
-    return uniform_f64(v);
-}
-template <int TPB> __device__ __forceinline__ double wmax(double v, double *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    if constexpr (TPB > 64) {
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double t = red[0];
-        for (int w = 1; w < TPB / 64; w++) t = fmax(t, red[w]);
-        v = t;
-    }
-    return uniform_f64(v);
-}
-template <int TPB> __device__ __forceinline__ double wmin(double v, double *red) { return -wmax<TPB>(-v, red); }
 
 // ---- the simple bounds of the swarm NLP (C6:349-352); thb: the heading is bounded as well (kernel 1 passes P.thb, the others their THB)
 __device__ __forceinline__ double lbu(const KParams &P, int c) { return (c & 1) ? -P.wmax : -P.vmax; }      // lower bound of control c (the upper one is its negative)
@@ -327,41 +302,6 @@ __device__ __forceinline__ void write_result(size_t inst, double obj, int status
     if (status_out) status_out[inst] = status;
     if (iters_out) iters_out[inst] = iters;
     if (kkt_out) kkt_out[inst] = kkt;
-}
-
-// Sum of log(s_i), s_i > 0, accumulated as (product of the mantissas, sum of the exponents): four instructions per term instead of a
-// logarithm (~90), one logarithm per wavefront at the end.  The mantissa product is renormalised after every term (no underflow however
-// many terms); a term <= 0 or NaN makes the result NaN, as the logarithm would.
-struct LogSum {
-    double m = 1.0, lo = INFINITY;
-    int e = 0;
-    __device__ __forceinline__ void add(double s_)
-    {
-        const double t = m * __builtin_amdgcn_frexp_mant(s_);
-        e += __builtin_amdgcn_frexp_exp(s_) + __builtin_amdgcn_frexp_exp(t);
-        m = __builtin_amdgcn_frexp_mant(t);
-        lo = fmin(lo, s_);
-    }
-};
-template <int TPB> __device__ __forceinline__ double wlogsum(LogSum a, double *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = a.m * __shfl_xor(a.m, o);
-        a.e += __shfl_xor(a.e, o) + __builtin_amdgcn_frexp_exp(t);
-        a.m = __builtin_amdgcn_frexp_mant(t);
-        a.lo = fmin(a.lo, __shfl_xor(a.lo, o));
-    }
-    double v = (a.lo > 0.0) ? fma((double)a.e, 0.693147180559945309417, log(a.m)) : NAN;
-    if constexpr (TPB > 64) {
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double t = 0.0;
-        for (int w = 0; w < TPB / 64; w++) t += red[w];
-        v = t;
-    }
-    return uniform_f64(v);
 }
 
 #ifdef NMPC_PROFILE

@@ -25,6 +25,35 @@
 
 namespace nmpc {
 
+// Where one instance keeps its arrays in LDS, in doubles from the start of dynamic LDS, for a workgroup of tpb threads.  The kernel, the poison
+// fill of its debug build and lds_bytes all take the layout from here.
+template <int M_, int THB> struct LdsLayout {
+    using G = G2<M_, THB>;
+    // W1 = [Pf | PV | Gb] and W2 = [UR | INV | PK] are only live during the Riccati sweep: the step and the adjoint residuals overlay them (below)
+    static constexpr int W1S = G::NX * G::NX + G::NX + G::NX * G::LDG, W2S = G::NU * G::LD + G::NU + G::PACK;
+    static_assert(G::KTS <= W2S, "the forward sweep stages a stage factor in W2");
+    int X, U, LAM, SPp, ZPp, SO, ZO, ZUL, ZUU, ZXL, ZXU, SUL, SUU, SN, CS;      // the iterate (sizes: see the kernel)
+    int Pf, PV, Gb, UR, INV, PK, D0, XS, RED;                                   // W1, W2, [NU], [NX], [8]
+    bool ovA, ovB;                   // the step [DX | DU] fits W1 / the residuals RV fit W2: they live there, else behind RED
+    int DX, DU, RV, ACT, total;      // ACT: [ceil(NT / tpb) * tpb] 16-bit words, the element ownership table; total: doubles of the whole
+    __host__ __device__ LdsLayout(int N, int K, int tpb)
+    {
+        const int N1 = N + 1, MK = M_ * K, NX = G::NX, NU = G::NU, NP = G::NP, NXB = G::NXB;
+        X = 0; U = X + N1 * NX; LAM = U + N * NU; SPp = LAM + N1 * NX; ZPp = SPp + N1 * NP; SO = ZPp + N1 * NP; ZO = SO + N1 * MK; ZUL = ZO + N1 * MK;
+        ZUU = ZUL + N * NU; ZXL = ZUU + N * NU; ZXU = ZXL + N1 * NXB; SUL = ZXU + N1 * NXB; SUU = SUL + N * NU; SN = SUU + N * NU; CS = SN + N * M_;
+        Pf = CS + N * M_; PV = Pf + NX * NX; Gb = PV + NX; UR = Gb + NX * G::LDG; INV = UR + NU * G::LD; PK = INV + NU; D0 = PK + G::PACK; XS = D0 + NU;
+        RED = XS + NX;
+        int extra = RED + 8;
+        ovA = N1 * NX + N * NU <= W1S; ovB = N1 * NX <= W2S;
+        DX = ovA ? Pf : extra; DU = DX + N1 * NX;
+        if (!ovA) extra += N1 * NX + N * NU;
+        RV = ovB ? UR : extra;
+        if (!ovB) extra += N1 * NX;
+        ACT = extra;
+        total = ACT + ((G::NT + tpb - 1) / tpb * tpb * 2 + 7) / 8;
+    }
+};
+
 template <int M_, int THB, int TPB>
 __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const double *__restrict__ p_in, const double *__restrict__ w0,
                                                          double *__restrict__ w_out, double *__restrict__ obj_out,
@@ -32,6 +61,7 @@ __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const d
                                                          double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
 {
     using G = G2<M_, THB>;
+    using W = WsLayout<M_, THB>;
     constexpr int NX = G::NX, NU = G::NU, NP = G::NP, NZ = G::NZ, LD = G::LD, NXB = G::NXB, NT = G::NT;
     constexpr int NTP = (NT + TPB - 1) / TPB;
     constexpr int HG = (TPB / NZ) > 0 ? (TPB / NZ) : 1;   // row groups of the G pass (thread -> column, rows strided)
@@ -44,48 +74,45 @@ __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const d
     const int NPA = prs ? G::NP : 0;
 
     extern __shared__ double sm[];
-    double *X = sm;                       // [N1*NX]
-    double *U = X + N1 * NX;              // [N*NU]
-    double *LAM = U + N * NU;             // [N1*NX]   lam[k] pairs with defect c_{k-1}
-    double *SPp = LAM + N1 * NX;          // [N1*NP]   pair slacks
-    double *ZPp = SPp + N1 * NP;          // [N1*NP]   pair duals
-    double *SO = ZPp + N1 * NP;           // [N1*MK]   obstacle slacks
-    double *ZO = SO + N1 * MK;            // [N1*MK]
-    double *ZUL = ZO + N1 * MK;           // [N*NU]
-    double *ZUU = ZUL + N * NU;           // [N*NU]
-    double *ZXL = ZUU + N * NU;           // [N1*NXB]
-    double *ZXU = ZXL + N1 * NXB;         // [N1*NXB]
-    double *SUL = ZXU + N1 * NXB;         // [N*NU]    explicit slacks of the simple bounds: s = u - lb computed on the fly
-    double *SUU = SUL + N * NU;           // [N*NU]    loses all relative accuracy once s ~ 1e-12 (active bound at mu = 1e-9)
-    double *SN = SUU + N * NU;            // [N*M]      (state-bound slacks are implicit: s = x + b, b - x; |x| <= 10 keeps them O(1) accurate)
-    double *CS = SN + N * M_;             // [N*M]
-    double *Pf = CS + N * M_;             // [NX*NX]   cost-to-go Hessian P (full symmetric storage)
-    double *PV = Pf + NX * NX;            // [NX]      cost-to-go gradient p
-    double *Gb = PV + NX;                 // [NX*LDG]  P [B A] and, in column NZ, p + P b
-    double *UR = Gb + NX * G::LDG;        // [NU*LD]   published pivot rows
-    double *INV = UR + NU * LD;           // [NU]      reciprocal pivots (contiguous with UR: streamed out together)
-    double *PK = INV + NU;                // [PACK]    current stage pack
-    double *D0 = PK + G::PACK;            // [NU]      pivots as assembled
-    double *XS = D0 + NU;                 // [NX]
-    double *RED = XS + NX;                // [8]
+    const LdsLayout<M_, THB> L(N, K, TPB);
+    double *X = sm + L.X;                 // [N1*NX]
+    double *U = sm + L.U;                 // [N*NU]
+    double *LAM = sm + L.LAM;             // [N1*NX]   lam[k] pairs with defect c_{k-1}
+    double *SPp = sm + L.SPp;             // [N1*NP]   pair slacks
+    double *ZPp = sm + L.ZPp;             // [N1*NP]   pair duals
+    double *SO = sm + L.SO;               // [N1*MK]   obstacle slacks
+    double *ZO = sm + L.ZO;               // [N1*MK]
+    double *ZUL = sm + L.ZUL;             // [N*NU]
+    double *ZUU = sm + L.ZUU;             // [N*NU]
+    double *ZXL = sm + L.ZXL;             // [N1*NXB]
+    double *ZXU = sm + L.ZXU;             // [N1*NXB]
+    double *SUL = sm + L.SUL;             // [N*NU]    explicit slacks of the simple bounds: s = u - lb computed on the fly
+    double *SUU = sm + L.SUU;             // [N*NU]    loses all relative accuracy once s ~ 1e-12 (active bound at mu = 1e-9)
+    double *SN = sm + L.SN;               // [N*M]      (state-bound slacks are implicit: s = x + b, b - x; |x| <= 10 keeps them O(1) accurate)
+    double *CS = sm + L.CS;               // [N*M]
+    double *Pf = sm + L.Pf;               // [NX*NX]   cost-to-go Hessian P (full symmetric storage)
+    double *PV = sm + L.PV;               // [NX]      cost-to-go gradient p
+    double *Gb = sm + L.Gb;               // [NX*LDG]  P [B A] and, in column NZ, p + P b
+    double *UR = sm + L.UR;               // [NU*LD]   published pivot rows
+    double *INV = sm + L.INV;             // [NU]      reciprocal pivots (contiguous with UR: streamed out together)
+    double *PK = sm + L.PK;               // [PACK]    current stage pack
+    double *D0 = sm + L.D0;               // [NU]      pivots as assembled
+    double *XS = sm + L.XS;               // [NX]
+    double *RED = sm + L.RED;             // [8]
     // Overlays.  W1 = [Pf | PV | Gb] and W2 = [UR | INV | PK] are only live during the Riccati sweep; the step (DX, DU) is
     // produced after it and consumed before the next one, so it lives in W1 when it fits; the stage residuals RV of the
     // adjoint recursion and the forward-sweep staging of the factors live in W2.
-    constexpr int W1S = NX * NX + NX + NX * G::LDG, W2S = NU * LD + NU + G::PACK;
-    double *extra = RED + 8;
-    const bool ovA = N1 * NX + N * NU <= W1S, ovB = N1 * NX <= W2S;
-    double *DX = ovA ? Pf : extra;        // [N1*NX]
-    double *DU = DX + N1 * NX;            // [N*NU]
-    if (!ovA) extra += N1 * NX + N * NU;
-    double *RV = ovB ? UR : extra;        // [N1*NX]   stage residuals / QP multipliers of the adjoint recursion (ACT follows, see below)
+    double *DX = sm + L.DX;               // [N1*NX]
+    double *DU = sm + L.DU;               // [N*NU]
+    double *RV = sm + L.RV;               // [N1*NX]   stage residuals / QP multipliers of the adjoint recursion
     double *FS = UR;                      // forward-sweep staging of one stage factor ([UR rows | INV], KTS doubles <= W2S)
 
     double *gpack = ws + inst * P.stride2 + P.oPACK;   // [N][PACK] + terminal [2*NX]
     double *gkt = ws + inst * P.stride2 + P.oKT;       // [N][KTS]
     double *TPp = ws + inst * P.stride2 + P.oELAS;     // [N1*NP]  elastic variables of the pair rows (elastic phase only), obstacle rows behind them
-    double *TOb = TPp + N1 * NP;                       // [N1*MK]
+    double *TOb = TPp + W::el_pair(N1);                     // [N1*MK]
     const double rho = P.rho_el;
-    double *gck = ws + inst * P.stride2 + P.oCKPT;     // saved cost-to-go [P | p] of the backward sweep, one slot of (NX + 1) * 64 doubles per NMPC_CKPT_EVERY stages
+    double *gck = ws + inst * P.stride2 + P.oCKPT;     // saved cost-to-go [P | p] of the backward sweep, one slot of W::CKPT_SLOT doubles per NMPC_CKPT_EVERY stages, W::CKPT_PP of them used
     const double *pp = p_in + inst * (2 * NX);
     const double *wi = w0 + inst * (size_t)P.nvar;
     double *wo = w_out + inst * (size_t)P.nvar;
@@ -107,12 +134,11 @@ __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const d
     // per-element offset tables are rebuilt from it at the start of every sweep, so they only occupy registers while
     // a sweep runs (kept for the whole kernel they cost ~100 VGPRs in every other phase and pushed the kernel into scratch).
     const int oUR = (int)(UR - sm) * 8, oGb = (int)(Gb - sm) * 8, oPK = (int)(PK - sm) * 8, oPf = (int)(Pf - sm) * 8;
-    unsigned short *ACT = reinterpret_cast<unsigned short *>(extra + ((ovB ? 0 : N1 * NX)));    // [NTP*TPB]
+    unsigned short *ACT = reinterpret_cast<unsigned short *>(sm + L.ACT);    // [NTP*TPB]
 #ifdef NMPC_POISON
     {   // debug build: every LDS word and the instance's HBM workspace start as NMPC_POISON, so that a read of anything this
         // solve did not write shows up as a parity failure instead of depending on what ran on the CU before
-        const int nl = (int)(reinterpret_cast<double *>(ACT) - sm) + (NTP * TPB * 2 + 7) / 8;
-        for (int e = tid; e < nl; e += TPB) sm[e] = NMPC_POISON;
+        for (int e = tid; e < L.total; e += TPB) sm[e] = NMPC_POISON;
         for (int e = tid; e < P.stride2; e += TPB) ws[inst * P.stride2 + e] = NMPC_POISON;
         __syncthreads();
     }
@@ -554,8 +580,8 @@ __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const d
                 }
                 for (int r = tid; r < NX; r += TPB) PV[r] = pkN[G::PK_G + NU + r];
             } else {
-                const double *ck = gck + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * ((NX + 1) * 64);
-                for (int e = tid; e < NX * NX + NX; e += TPB) Pf[e] = ck[e];
+                const double *ck = gck + (size_t)((N - 1 - kst) / NMPC_CKPT_EVERY) * W::CKPT_SLOT;
+                for (int e = tid; e < W::CKPT_PP; e += TPB) Pf[e] = ck[e];
             }
             // ---- per-element LDS byte offsets (relative to sm): pivot-row entries UR[.][a], UR[.][c]; the three G entries,
             //      the coefficient triple and the Hessian addition of the assembly; the mirror positions of the Schur block
@@ -602,8 +628,8 @@ __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const d
             lds_sync<TPB>();
             for (int k = kst; k >= 0; k--) {
                 if (k < kst && (kst - k) % NMPC_CKPT_EVERY == 0) {      // save [P | p] entering this stage
-                    double *ck = gck + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * ((NX + 1) * 64);
-                    for (int e = tid; e < NX * NX + NX; e += TPB) ck[e] = Pf[e];
+                    double *ck = gck + (size_t)((N - 1 - k) / NMPC_CKPT_EVERY) * W::CKPT_SLOT;
+                    for (int e = tid; e < W::CKPT_PP; e += TPB) ck[e] = Pf[e];
                 }
                 // ---- stage pack -> LDS; prefetch the next one
 #pragma unroll
@@ -1080,14 +1106,7 @@ __global__ __launch_bounds__(TPB) void solve_lds_kernel(const KParams P, const d
 // LDS bytes of one instance
 template <int M_, int THB> static size_t lds_bytes(const KParams &P, int tpb)
 {
-    using G = G2<M_, THB>;
-    const size_t N = P.N, N1 = P.N + 1, MK = (size_t)M_ * P.K;
-    const size_t W1S = (size_t)G::NX * G::NX + G::NX + (size_t)G::NX * G::LDG, W2S = (size_t)G::NU * G::LD + G::NU + G::PACK;
-    size_t d = N1 * G::NX * 2 + N * G::NU * 5 + N1 * G::NP * 2 + N1 * MK * 2 + N1 * G::NXB * 2 + N * M_ * 2 + W1S + W2S + G::NU + G::NX + 8;
-    if (N1 * G::NX + N * G::NU > W1S) d += N1 * G::NX + N * G::NU;      // step does not fit the Riccati working area
-    if (N1 * G::NX > W2S) d += N1 * G::NX;
-    d += ((size_t)((G::NT + tpb - 1) / tpb) * tpb * 2 + 7) / 8;      // 16-bit element table
-    return d * sizeof(double);
+    return (size_t)LdsLayout<M_, THB>(P.N, P.K, tpb).total * sizeof(double);
 }
 
 template <int M_, int THB, int TPB> static hipError_t launch2_mtt(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
@@ -1164,17 +1183,6 @@ size_t lds_kernel_bytes(const KParams &P, int m)
         constexpr int M_ = decltype(M)::value;
         return P.thb ? lds_bytes<M_, 1>(P, lds_tp_threads<M_>()) : lds_bytes<M_, 0>(P, lds_tp_threads<M_>());
     });
-}
-
-// workspace doubles per instance for this kernel (packs + transposed gains)
-void lds_kernel_workspace(const KParams &P, int m, int64_t *pack_off, int64_t *kt_off, int64_t *stride)
-{
-    const int64_t pack = for_team_size(m, (int64_t)0, [&](auto M) { return (int64_t)(P.thb ? G2<decltype(M)::value, 1>::PACK : G2<decltype(M)::value, 0>::PACK); });
-    const int64_t kts = for_team_size(m, (int64_t)0, [&](auto M) { return (int64_t)(P.thb ? G2<decltype(M)::value, 1>::KTS : G2<decltype(M)::value, 0>::KTS); });
-    int64_t o = 0;
-    *pack_off = o; o += (int64_t)(P.N + 1) * pack; o = (o + 15) / 16 * 16;
-    *kt_off = o; o += (int64_t)P.N * kts; o = (o + 15) / 16 * 16;
-    *stride = o;
 }
 
 }  // namespace nmpc
