@@ -268,6 +268,37 @@ int32_t nmpc_kkt_batch(nmpc_handle_t *h, int32_t B, const double *p, const doubl
                        const double *lam_x, double *res /* [B][6] */, double *grad_lag /* [B][n_var] or NULL */, void *stream);
 
 /*
+ * Plan sensitivities and feedback gains: how the plan moves when the measured state or the goal moves, d w* / d p, and its first block
+ * d U_0* / d x0 — the linear feedback around a plan that runs between two solves, and the correction of advanced-step NMPC.
+ *
+ * Definition: the linearisation of the solver's own barrier KKT system at a given primal-dual point.  Inputs (p, w, lam_g, lam_x) in the
+ * layouts and the sign convention above (a solve's outputs, or any others), (obs, obs_stages) by the rules of nmpc_kkt_batch.  W is
+ *   the exact Lagrangian Hessian grad^2 f + sum_i lam_g,i grad^2 g_i (2 Q, 2 R, the heading / speed curvature of the defects, the pair and
+ *   obstacle blocks)
+ *   + for every inequality row of stages 1..N-1: grad g_i Sigma_i grad g_i' with Sigma_i = z_i / s_i, z_i = max(-lam_g,i, 0), s_i = g_i - lbg_i
+ *   + for every finite variable bound of X_1..X_N and U: max(lam_x, 0) / (ub - w) + max(-lam_x, 0) / (w - lb) on the diagonal;
+ *   the pair and obstacle rows of stage 0, the pad rows and X_0 carry nothing (the structural zeros of the multipliers above).
+ * The equality rows are the initial block and the defects, linearised: dX_0 = dx0, dX_{k+1} = A_k dX_k + B_k dU_k.  For dp = [dx0; dxs],
+ * dw minimises 1/2 dw' W dw - sum_{k<N} (2 Q dxs)' dX_k on those equalities.  At a converged point this is the derivative of the barrier
+ * solution at the solver's final mu: O(mu) from the NLP's own derivative wherever the NLP has one (where the active set changes it has none).
+ * Solved by the stage recursion P_N = the bound terms of X_N, F = [F_uu F_ux; F_xu F_xx] = W_k + [B A]' P_{k+1} [B A], G_k = -F_uu^-1 F_ux,
+ * without an inertia shift.
+ *   gains [B][S][n_u][n_x]  S = gain_stages, 1 or N: G_k = d U_k / d X_k along the plan, G_0 = d U_0* / d x0; S = 1 writes stage 0 only
+ *   dw    [B][n_var]        for dp [B][n_p]: dU_k = G_k dX_k + g_k, dX_0 = dx0 (copied)
+ *   info  [B]               0: success.  1: some F_uu has a pivot <= 0 — the point is not a strict minimiser of its barrier problem.
+ *                           2: a row or bound with a positive multiplier has s <= 0 (this verdict goes first).  With 1 or 2 the instance's
+ *                           gains and dw are written as zeros.
+ * gains and dw may each be NULL; dp == NULL requires dw == NULL; both NULL still computes info.  Saturated controls give gains near zero, a
+ * swarm pressed against a pair row large ones.
+ * Returns NMPC_E_ARG for null p, w, lam_g, lam_x or info with B > 0, gain_stages neither 1 nor N with gains != NULL, dw without dp, B beyond
+ * max_batch, and the field errors of the *_obs calls; NMPC_E_UNSUPPORTED on handles that run on kernel 1 or 2, as the *_duals calls (they
+ * cannot produce the multipliers either).  The inputs are read-only; the call is stream-ordered with the handle's other calls and uses the
+ * handle's workspace between its two passes (the one-handle-one-stream rule above covers it); no solve result depends on it.
+ */
+int32_t nmpc_sens_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                        const double *lam_x, const double *dp, double *dw, double *gains, int32_t gain_stages, int32_t *info, void *stream);
+
+/*
  * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and
  * nmpc_kkt_batch with the pose reference of every instance given apart from p, one row for the horizon or one per stage (the tutorial
  * lineage of the scripts carries it as P = [x0; x_ref,1 .. x_ref,N]; AS/mpc_control_trajectory_tracking.py tracks a path on its SLSQP route):

@@ -302,6 +302,34 @@ class NmpcSolver:
                                                self._stream()), "nmpc_kkt_batch")
         return (res, grad) if want_grad else res
 
+    def sens_batch(self, p, w, lam_g, lam_x, dp=None, gains=None, obstacles=None):
+        """Plan sensitivities and feedback gains of (w, lam_g, lam_x) for B instances on the device (nmpc_sens_batch): the linearisation of the
+        solver's barrier KKT system at that primal-dual point, as include/nmpc.h defines it — usually a solve's output with want_duals=True.
+        dp [B, n_p] = [dx0; dxs]: also return dw [B, n_var], the first-order change of the plan (w + dw predicts the solve at p + dp).
+        gains: None (no gains), 1 (G_0 = dU_0*/dx0 only, [B, 1, n_u, n_x]) or "N" / the horizon (G_k = dU_k/dX_k of every stage, [B, N, n_u, n_x]).
+        obstacles as in solve_batch.  Returns dict(dw, gains, info): info [B] int32 is 0 on success, 1 where the point is no strict minimiser
+        of its barrier problem, 2 where a row or bound with a positive multiplier has no slack; dw and gains of such an instance are zeros.
+        Needs a handle that returns multipliers (duals_supported()); the solver(x0=, p=, ...) call surface is unchanged."""
+        torch = self.torch
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        if gains not in (None, 1, "N", self.cfg.N):
+            raise ValueError(f'gains must be None, 1 or "N" (= {self.cfg.N}), got {gains!r}')
+        S = 0 if gains is None else (1 if gains == 1 else self.cfg.N)
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
+        dp = self._dev(dp, (B, self.n_p)) if dp is not None else None
+        dw = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device) if dp is not None else None
+        G = torch.empty((B, S, self.cfg.nu, self.cfg.nx), dtype=torch.float64, device=self.device) if S else None
+        info = torch.empty(B, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nmpc_sens_batch(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
+                                                w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), dp.data_ptr() if dp is not None else None,
+                                                dw.data_ptr() if dw is not None else None, G.data_ptr() if S else None, S if S else 1,
+                                                info.data_ptr(), self._stream()), "nmpc_sens_batch")
+        return dict(dw=dw, gains=G, info=info)
+
     def shift_batch(self, p, w, plant: bool = True):
         """device warm-start shift (C6:160-169,460-465) and, if plant, x0 + T f(x0,u0) (casadi_test.py:17-26)."""
         torch = self.torch
