@@ -275,15 +275,16 @@ def load_cases():
     return out
 
 
-def indefinite_point(cfg, w, lam_g, value=-60.0):
-    """lam_g with the defect multipliers of robot 0 at the last stage k >= 1 where it moves set so that the heading curvature
+def indefinite_point(cfg, w, lam_g, value=-60.0, robot=0):
+    """lam_g with the defect multipliers of robot `robot` at the last stage k >= 1 where it moves set so that the heading curvature
     T v (l_x cos th + l_y sin th) of that stage is `value` (the theta-v cross term T (l_x sin th - l_y cos th) stays 0): P_k gets a negative
-    heading entry and F_uu of stage k-1 turns negative through the omega -> theta coupling, T^2 P_k[th, th].  Returns (lam_g, k)."""
+    heading entry and F_uu of stage k-1 turns negative through the omega -> theta coupling, T^2 P_k[th, th] (the pivot of that robot's turn
+    rate: lane 2 robot + 1).  Returns (lam_g, k)."""
     X, U = R.unpack(cfg, w)
-    k = max(k for k in range(1, cfg.N) if abs(U[k, 0]) > 1e-3)
-    th, v = X[k, 2], U[k, 0]
+    k = max(k for k in range(1, cfg.N) if abs(U[k, 2 * robot]) > 1e-3)
+    th, v = X[k, 3 * robot + 2], U[k, 2 * robot]
     out = np.array(lam_g, float)
-    o = cfg.rows0 + k * cfg.rows_k
+    o = cfg.rows0 + k * cfg.rows_k + 3 * robot
     out[o] = value * np.cos(th) / (cfg.T * v); out[o + 1] = value * np.sin(th) / (cfg.T * v)
     return out, k
 
