@@ -71,6 +71,7 @@ typedef struct {
     int el;         /* 1 while the solve is in its elastic phase (the second restart of last resort): pair / obstacle rows h + t - s = 0, t >= 0, penalty NMPC_ELASTIC_RHO t */
     double rho;
     double *El, *Elt, *dEl;      /* elastic variables t, trial, step */
+    int ld_cold, ld_restart, ld_el;   /* the ladder of the last solve: cold retries begun, barrier restarts, iterations spent with el set (nmpc_oracle_ladder_stats) */
     int max_restarts;   /* barrier restarts after a stall: 3 (as the HIP path); NMPC_ORACLE_MAX_RESTARTS overrides (fixture generation) */
     int o_ul, o_uu, o_xl, o_xu, o_pr, o_ob;
     double T, dmin2, vmax, wmax, xymax, thmax, robdim, margin;
@@ -397,6 +398,15 @@ void nmpc_oracle_stats(double *out, int reset)
     if (reset) { g_stat_fact = g_stat_iter = g_stat_mod = g_stat_stages = 0; }
 }
 
+/* Ladder counters per instance (test aid): after nmpc_oracle_ladder_stats(buf, B) every solve_batch / solve_batch_obs call writes, for each
+   instance b < B, buf[3 b .. 3 b + 2] = cold retries begun, barrier restarts, iterations spent in the elastic phase.  NULL ends it. */
+static int32_t *g_ladder = NULL;
+static int32_t g_ladder_cap = 0;
+void nmpc_oracle_ladder_stats(int32_t *buf, int32_t B)
+{
+    g_ladder = buf; g_ladder_cap = buf ? B : 0;
+}
+
 /* (Re)start of the barrier iteration from the current primal point, or — cold != 0 — from the reference's cold start
    X_k = x0, U = 0 (C6:398-400): the point goes strictly inside the simple bounds, slacks onto the constraint values, duals mu/s,
    multipliers 0.  Returns the objective. */
@@ -452,6 +462,7 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
 
     /* stage-0 pair / obstacle rows act on the pinned state: feasibility pre-check */
     int infeasible = 0;
+    w->ld_cold = w->ld_restart = w->ld_el = 0;
     for (int pq = 0; pq < w->M; pq++) {
         int i = w->pi[pq], j = w->pj[pq];
         double dx = x0p[3 * i] - x0p[3 * j], dy = x0p[3 * i + 1] - x0p[3 * j + 1];
@@ -492,9 +503,11 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
     const int max_cold = (getenv("NMPC_ORACLE_NO_COLD_RETRY") || w->ipopt) ? 0 : (getenv("NMPC_ORACLE_MAX_COLD") ? atoi(getenv("NMPC_ORACLE_MAX_COLD")) : NMPC_COLD_RETRIES);
     int n_cold = 0;
     int it_base = 0;      /* iteration at which the current attempt started (watchdog reference) */
+    int it_el = 0;        /* iteration at which the elastic phase started */
 #define COLD_RETRY()                                                                                                              \
     do {                                                                                                                          \
         n_cold++; it_base = it; w->el = n_cold >= 2; mu = w->mu_init; f = barrier_restart(w, xs, mu, 1);                          \
+        w->ld_cold = n_cold; if (n_cold == 2) it_el = it;                                                                         \
         delta_last = 0.0; nu_pen = 1.0; need_shift = 0; mcount = 0; n_tiny = 0; n_restart = 0;                                    \
         memset(w->dl_k, 0, sizeof(double) * (size_t)N * nu); memset(w->ns_k, 0, sizeof(int) * (size_t)N * nu);                    \
     } while (0)
@@ -1004,7 +1017,7 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
             /* barrier restart from the current primal point (a restoration phase in miniature): slacks back onto the
                constraint values, duals mu/s, multipliers 0, barrier parameter back to at least mu_init.  Rescues 15 of 16
                captured stalls of the six-robot + eight-obstacle composite. */
-            n_restart++; n_tiny = 0;
+            n_restart++; n_tiny = 0; w->ld_restart++;
             mu = fmax(mu, w->mu_init);
             f = barrier_restart(w, xs, mu, 0);
             delta_last = 0.0; nu_pen = 1.0; need_shift = 0; mcount = 0;
@@ -1014,6 +1027,7 @@ static int solve_one(ws_t *w, const double *p, const double *w0, double *wout, d
     memcpy(wout, w->X, sizeof(double) * (size_t)(N + 1) * nx);
     memcpy(wout + (size_t)(N + 1) * nx, w->U, sizeof(double) * (size_t)N * nu);
     *obj_out = f; *iters_out = it; *kkt_out = kkt;
+    w->ld_el = w->el ? it - it_el : 0;
     return status;
 }
 
@@ -1044,6 +1058,7 @@ static int32_t solve_batch_field(const nmpc_config_t *cfg, int32_t B, const doub
             if (status) status[b] = st;
             if (iters) iters[b] = it;
             if (kkt) kkt[b] = k;
+            if (g_ladder && b < g_ladder_cap) { g_ladder[3 * b] = w->ld_cold; g_ladder[3 * b + 1] = w->ld_restart; g_ladder[3 * b + 2] = w->ld_el; }
         }
         ws_free(w);
     }

@@ -47,6 +47,8 @@ def lib():
         _LIB.nmpc_oracle_eval_batch_obs.restype = C.c_int32
         _LIB.nmpc_oracle_shift_batch.argtypes = [C.POINTER(Config), C.c_int32, dp, dp, dp, dp]
         _LIB.nmpc_oracle_max_threads.restype = C.c_int32
+        _LIB.nmpc_oracle_ladder_stats.argtypes = [ip, C.c_int32]
+        _LIB.nmpc_oracle_ladder_stats.restype = None
         for f in ("nmpc_oracle_n_var", "nmpc_oracle_n_g", "nmpc_oracle_n_p"):
             getattr(_LIB, f).argtypes = [C.POINTER(Config)]
             getattr(_LIB, f).restype = C.c_int32
@@ -142,6 +144,18 @@ def shift_batch(cfg: Config, p: np.ndarray, w: np.ndarray, plant: bool = True):
     wn = np.empty_like(w); x0n = np.empty((B, 3 * cfg.m))
     L.nmpc_oracle_shift_batch(C.byref(cfg), B, _dp(p), _dp(w), _dp(wn), _dp(x0n) if plant else None)
     return wn, (x0n if plant else None)
+
+
+def with_ladder_stats(B: int, solve):
+    """solve() (one solve_batch / solve_batch_obs call of B instances) with the oracle's ladder counters on: (its result, [B, 3] int32 of cold
+    retries begun, barrier restarts and iterations spent in the elastic phase, per instance)"""
+    L = lib()
+    buf = np.zeros((B, 3), dtype=np.int32)
+    L.nmpc_oracle_ladder_stats(buf.ctypes.data_as(C.POINTER(C.c_int32)), B)
+    try:
+        return solve(), buf
+    finally:
+        L.nmpc_oracle_ladder_stats(None, 0)
 
 
 def max_threads() -> int:
