@@ -299,6 +299,38 @@ int32_t nmpc_sens_batch(nmpc_handle_t *h, int32_t B, const double *p, const doub
                         const double *lam_x, const double *dp, double *dw, double *gains, int32_t gain_stages, int32_t *info, void *stream);
 
 /*
+ * Adjoint plan sensitivities: the gradient of a scalar l(w*) with respect to the measured state, the goal and the per-instance obstacle field
+ * from ONE launch, where the call above needs one launch per direction (n_p = 36 for six robots, N K 3 obstacle entries per instance).
+ *
+ * Notation as above: W is the barrier-augmented Lagrangian Hessian at (w, lam_g, lam_x), the equalities are the initial block and the
+ * linearised defects, and S_p : dp -> dw is the map nmpc_sens_batch defines.  The obstacle map S_o : dobs -> dw, for a change dobs [S][K][3] of
+ * the instance's field: dw minimises 1/2 dw' W dw + (M_o dobs)' dw on the homogeneous equalities (dX_0 = 0, linearised defects).  M_o collects
+ * one contribution per obstacle row i = (k, robot, o) of stages k = 1..N-1 (the rows of stage 0 carry nothing, as everywhere else).  With e the
+ * obstacle's entry at stage k (entry k when S == N, entry 0 when S == 1), ex = x - e.ox, ey = y - e.oy, rr = sqrt(ex^2 + ey^2), n = (ex, ey) / rr,
+ * l = lam_g,i, s = rr - rob_dim - e.r - margin and Sigma = max(-l, 0) / s, the block of M_o in rows (x, y) of that robot at stage k is
+ *   columns (ox, oy):  -l (I - n n') / rr - Sigma n n'
+ *   column r:          -Sigma n
+ * — d/do of the barrier stationarity condition, lam d_o grad g + grad g Sigma d_o g with d_o g = (-n', -1).
+ *
+ * For a cotangent wbar [B][n_var] of the plan the call returns the transposes:
+ *   pbar   [B][n_p]      = S_p' wbar   (x0 half, then xs half)
+ *   obsbar [B][S][K][3]  = S_o' wbar   S = obs_stages of the call; S == 1 sums the stages that share entry 0; entry 0 is exactly zero when S == N
+ *   info   [B]           the verdicts of nmpc_sens_batch (2 first, then 1); with 1 or 2 the instance's outputs are zeros
+ * Equivalently: let v minimise 1/2 v' W v - wbar' v on the homogeneous equalities; then pbar_xs = sum_{k<N} 2 Q v_{X_k}, obsbar = -M_o' v, and
+ * pbar_x0 is the multiplier of that QP's initial block (minus the affine part of the stage-0 cost-to-go of the backward recursion).  The
+ * defining identity is <pbar, dp> = <wbar, S_p dp> for every dp, and <obsbar, dobs> = <wbar, S_o dobs> for every dobs.  Sums over robots that
+ * share an obstacle and over stages that share an entry run in a fixed order: the same inputs give the same bits.
+ *
+ * pbar and obsbar may each be NULL (both NULL still computes info).  obsbar != NULL with obs == NULL is NMPC_E_ARG: the handle's own field is
+ * not a per-instance parameter.  The other argument errors are those of nmpc_sens_batch (null p, w, lam_g, lam_x, wbar or info with B > 0,
+ * B beyond max_batch, the field errors of the *_obs calls), NMPC_E_UNSUPPORTED on handles that run on kernel 1 or 2.  The inputs are
+ * read-only; the call is stream-ordered with the handle's other calls and uses the handle's workspace between its two passes exactly as
+ * nmpc_sens_batch does (nmpc_workspace_bytes does not change); no solve result depends on it.
+ */
+int32_t nmpc_sens_adjoint_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                                const double *lam_x, const double *wbar, double *pbar, double *obsbar, int32_t *info, void *stream);
+
+/*
  * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and
  * nmpc_kkt_batch with the pose reference of every instance given apart from p, one row for the horizon or one per stage (the tutorial
  * lineage of the scripts carries it as P = [x0; x_ref,1 .. x_ref,N]; AS/mpc_control_trajectory_tracking.py tracks a path on its SLSQP route):

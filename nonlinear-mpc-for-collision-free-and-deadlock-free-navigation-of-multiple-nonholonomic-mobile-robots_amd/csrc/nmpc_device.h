@@ -103,6 +103,10 @@ hipError_t launch_kkt(const KParams &P, const PoseRef &xr, int m, int B, const d
 // nullptr, info [B]; ws: the workspace of a handle that runs on the column kernel (its pivot-row region holds [G_k | g_k] between the two passes)
 hipError_t launch_sens(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *dp, double *dw, double *gains,
                        int gain_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
+// the transposes of the same maps applied to wbar [B][nvar] (include/nmpc.h, nmpc_sens_adjoint_batch; nmpc_sens_adj.hip): pbar [B][2 nx] and
+// obsbar [B][obs_stages][K][3], each or both nullptr (obsbar only with ofield); info and ws as launch_sens
+hipError_t launch_sens_adjoint(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *wbar, double *pbar,
+                               double *obsbar, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);
 hipError_t launch_odometry(long n, const double *odom, const double *init, double *pose, int wrap, hipStream_t st);

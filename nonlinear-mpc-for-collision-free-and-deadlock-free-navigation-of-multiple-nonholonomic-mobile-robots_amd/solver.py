@@ -330,6 +330,37 @@ class NmpcSolver:
                                                 info.data_ptr(), self._stream()), "nmpc_sens_batch")
         return dict(dw=dw, gains=G, info=info)
 
+    def sens_adjoint_batch(self, p, w, lam_g, lam_x, wbar, obstacles=None, want_pbar: bool = True, want_obsbar: Optional[bool] = None):
+        """Adjoint plan sensitivities of (w, lam_g, lam_x) for B instances on the device (nmpc_sens_adjoint_batch): for a cotangent wbar [B, n_var] of
+        the plan — the gradient of a scalar l(w*) — one launch returns pbar [B, n_p] = (dw*/dp)' wbar (x0 half, then xs half) and, with a
+        per-instance obstacle field, obsbar = (dw*/dobstacles)' wbar in the shape of `obstacles` ([B, K, 3]: summed over the stages that share the
+        entry; [B, N, K, 3]: entry 0 is zero), by the linearisation sens_batch uses.  obstacles as in solve_batch; without it obsbar is None (the
+        config's own field is no per-instance parameter).  want_pbar / want_obsbar switch an output off (None; the other keeps its bits).
+        Returns dict(pbar, obsbar, info): info [B] int32 as in sens_batch; the outputs of an instance with info != 0 are zeros.
+        Needs a handle that returns multipliers (duals_supported())."""
+        torch = self.torch
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
+        wbar = self._dev(wbar, (B, self.n_var))
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
+        if want_obsbar is None:
+            want_obsbar = ob is not None
+        if want_obsbar and ob is None:
+            raise ValueError("obsbar needs obstacles=: the config's own field is not a per-instance parameter")
+        pbar = torch.empty((B, self.n_p), dtype=torch.float64, device=self.device) if want_pbar else None
+        obsbar = torch.empty(tuple(ob[0].shape), dtype=torch.float64, device=self.device) if want_obsbar else None
+        info = torch.empty(B, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nmpc_sens_adjoint_batch(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
+                                                        w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), wbar.data_ptr(),
+                                                        pbar.data_ptr() if want_pbar else None, obsbar.data_ptr() if want_obsbar else None,
+                                                        info.data_ptr(), self._stream()), "nmpc_sens_adjoint_batch")
+        if obsbar is not None and len(getattr(obstacles, "shape", np.shape(obstacles))) == 3:
+            obsbar = obsbar.reshape(B, len(self.cfg.obstacles), 3)
+        return dict(pbar=pbar, obsbar=obsbar, info=info)
+
     def shift_batch(self, p, w, plant: bool = True):
         """device warm-start shift (C6:160-169,460-465) and, if plant, x0 + T f(x0,u0) (casadi_test.py:17-26)."""
         torch = self.torch
