@@ -91,6 +91,13 @@ def last_build_info() -> dict:
         return {}
 
 
+def codegen_flags() -> list:
+    """The flags of build() that decide the device code of a translation unit, for whoever compiles a stand-alone program against the headers
+    of csrc/ (tests/probes/wave_probe.hip).  Pure: reads the environment, runs nothing.  tests/test_wave_probe_host.py holds every compile
+    command of build() against this list."""
+    return ["--offload-arch=gfx950", os.environ.get("NMPC_OPT", "-O3"), "-std=c++17"] + os.environ.get("NMPC_EXTRA_DEFS", "").split()
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     import time
     t0 = time.time()

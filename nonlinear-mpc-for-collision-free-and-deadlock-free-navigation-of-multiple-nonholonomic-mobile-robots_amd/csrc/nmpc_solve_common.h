@@ -170,7 +170,7 @@ template <int TPB> __device__ __forceinline__ void lds_sync()
 }
 
 // reciprocal of a pivot: v_rcp_f64 seed + Newton steps.  NMPC_RCP_STEPS = 1 (round 4): the seed is good to about single precision, one step
-// leaves ~1e-14 relative — the factorisation of an interior-point step does not need more (iteration counts of the bench batches equal to
+// leaves <= 2.0e-15 relative (1.9e-15 measured, docs/WAVE_PRIMITIVES.md) — the factorisation of an interior-point step does not need more (iteration counts of the bench batches equal to
 // 1e-5 relative, parity tests unchanged) and the two dependent multiply-adds it saves sit on the pivot chain of every stage: A/B in one
 // session, six robots B=4096 +2.3 %, B=16384 +1.2 %.  2 = full fp64 accuracy (rounds 2-3; rcp2 of nmpc_wave.h, which the LIDAR kernel always takes).
 #ifndef NMPC_RCP_STEPS

@@ -7,7 +7,7 @@
 
 namespace nmpc {
 
-// reciprocal: v_rcp_f64 seed + ONE Newton step (the seed is good to about single precision: ~1e-14 relative after the step) ...
+// reciprocal: v_rcp_f64 seed + ONE Newton step (seed error e0 = 4.2e-8 measured; after the step <= e0^2 + 2u = 2.0e-15, 1.9e-15 measured: docs/WAVE_PRIMITIVES.md) ...
 __device__ __forceinline__ double rcp1(double d)
 {
     double r = __builtin_amdgcn_rcp(d);
@@ -22,9 +22,9 @@ __device__ __forceinline__ double rcp2(double d)
     return fma(fma(-d, r, 1.0), r, r);
 }
 // Divisions of the stage-parallel phases (sigma = z / s, mu / s, dz, the step-length quotients): NMPC_FAST_DIV = 1 replaces the IEEE division
-// chain (~12 instructions: div_scale x2, rcp, four multiply-adds, div_fmas, div_fixup) by rcp1 and a multiply (4): relative error <= 2.3e-15
-// against the division (tools/rcp_probe.hip).  Every site of one quantity goes through the same helper, so the sites stay consistent with
-// each other.  NMPC_FAST_DIV = 0 restores the divisions (A/B; the LIDAR source sets it from its own switch NMPC_LIDAR_FAST_DIV).
+// chain (~12 instructions: div_scale x2, rcp, four multiply-adds, div_fmas, div_fixup) by rcp1 and a multiply (4): relative error <= 2.1e-15
+// (e0^2 + 3u; 2.0e-15 measured, tests/probes/wave_probe.hip), NaN at a denominator 0, +-inf or below 2^-1024 where the division gives +-inf, +-0
+// or a finite value (docs/WAVE_PRIMITIVES.md).  Every site of one quantity goes through the same helper, so the sites stay consistent with each other.  NMPC_FAST_DIV = 0 restores the divisions (A/B; the LIDAR source sets it from its own switch NMPC_LIDAR_FAST_DIV).
 // A/B in one session (round 4): six robots B=4096 262 k -> 280 k solves/s, B=16384 388 k -> 410 k, a lone wave +10 %, mean iterations 29.0735 -> 29.0720.
 #ifndef NMPC_FAST_DIV
 #define NMPC_FAST_DIV 1
