@@ -331,6 +331,41 @@ int32_t nmpc_sens_adjoint_batch(nmpc_handle_t *h, int32_t B, const double *p, co
                                 const double *lam_x, const double *wbar, double *pbar, double *obsbar, int32_t *info, void *stream);
 
 /*
+ * Forward plan update: the first-order change of the plan when the measured state, the goal AND the per-instance obstacle field move between a
+ * solve and its use, dw = S_p dp + S_o dobs in one launch, with a step limit alpha that says how much of it keeps every linearised slack
+ * non-negative — the correction of advanced-step NMPC among moving obstacles.
+ *
+ * Notation as above.  (p, obs, obs_stages, w, lam_g, lam_x), W, the equalities, the verdicts (2 first, then 1) and the handle rules are exactly
+ * those of nmpc_sens_batch.  dw minimises 1/2 dw' W dw + c' dw subject to dX_0 = dx0 and the linearised defects, with the linear term
+ *   c = -2 Q dxs on X_k, k < N   +   M_o dobs   -   rhs
+ *   dp   [B][n_p]        = [dx0; dxs]
+ *   dobs [B][S][K][3]    S = obs_stages of the call: the change of the instance's field
+ *   rhs  [B][n_var]      a general linear term
+ * each may be NULL, which means zero.  M_o is the matrix defined under nmpc_sens_adjoint_batch: stage 0 carries nothing, entry 0 of a per-stage
+ * dobs is not read, and with S == 1 entry 0 acts at every stage 1..N-1.  With dobs == rhs == NULL the call defines the dw of nmpc_sens_batch;
+ * with only rhs = wbar it is the v of the adjoint call's text (pbar_xs = sum_{k<N} 2 Q v_{X_k}, obsbar = -M_o' v).  The terms of c at one entry
+ * are added in a fixed order — goal, then rhs, then the obstacles in index order: the same inputs give the same bits.
+ *   dw    [B][n_var]     dX_0 = dx0 (copied), dU_k = G_k dX_k + g_k along the linearised defects
+ *   alpha [B]            the largest a in (0, 1] for which every linearised slack stays non-negative along a (dw, dobs):
+ *                        alpha = min(1, min_i s_i / (-ds_i)) over the items with s_i > 0 and ds_i < 0.  The items are the pair and obstacle rows
+ *                        of stages 1..N-1 and both sides of every finite bound of X_1..X_N and U_0..U_{N-1}:
+ *                          pair row (i, a):   s = |xy_i - xy_a|^2 - d_min^2 with e = xy_i - xy_a,   ds = 2 e' (dxy_i - dxy_a)
+ *                          obstacle row:      s = rr - rob_dim - e.r - margin,                      ds = n' (dxy - doxy) - dr   (that stage's entry of dobs)
+ *                          upper bound:       s = ub - v,   ds = -dv;      lower bound:  s = v + ub,   ds = dv
+ *                        Left out: the rows of stage 0, the pad rows, X_0 and the items with s_i <= 0 (nmpc_kkt_batch reports those).
+ *                        alpha == 1.0 exactly when nothing limits the step.  No clipping of w + dw is done anywhere.
+ *   info  [B]            the verdicts of nmpc_sens_batch; with 1 or 2 the instance gets dw = 0 and alpha = 0
+ * dw and alpha may each be NULL (both NULL still computes info); each keeps its bits when the other is left out.
+ * dobs != NULL with obs == NULL is NMPC_E_ARG: the handle's own field is not a per-instance parameter.  The other argument errors are those of
+ * nmpc_sens_batch (null p, w, lam_g, lam_x or info with B > 0, B beyond max_batch, the field errors of the *_obs calls), NMPC_E_UNSUPPORTED on
+ * handles that run on kernel 1 or 2.  The inputs are read-only; the call is stream-ordered with the handle's other calls and uses the handle's
+ * workspace between its two passes exactly as nmpc_sens_batch does (nmpc_workspace_bytes does not change); no solve result depends on it.
+ */
+int32_t nmpc_sens_update_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                               const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw, double *alpha, int32_t *info,
+                               void *stream);
+
+/*
  * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and
  * nmpc_kkt_batch with the pose reference of every instance given apart from p, one row for the horizon or one per stage (the tutorial
  * lineage of the scripts carries it as P = [x0; x_ref,1 .. x_ref,N]; AS/mpc_control_trajectory_tracking.py tracks a path on its SLSQP route):

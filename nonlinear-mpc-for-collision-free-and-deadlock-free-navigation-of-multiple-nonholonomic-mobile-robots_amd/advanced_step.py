@@ -1,0 +1,69 @@
+"""Advanced-step NMPC among moving obstacles: solve ahead of time at the predicted state and field, then correct the plan with one cheap launch
+when the measurement arrives.
+
+prepare is one nmpc_solve_batch_duals launch, correct one nmpc_sens_update_batch launch on the solve's own primal-dual point (include/nmpc.h:
+dw = S_p dp + S_o dobs and the step limit alpha).  The correction is applied over step = 1 where nothing limits it and tau * alpha elsewhere, so
+that no linearised slack reaches zero; nothing is clipped.  torch carries the tensors; all arithmetic of the solve and of the update happens in
+libnmpc_hip.so.
+"""
+from __future__ import annotations
+
+from .solver import NmpcSolver
+
+
+class AdvancedStepController:
+    """ctl = AdvancedStepController(solver, tau=0.99); ctl.prepare(p_pred, w0, obstacles=obs_pred); out = ctl.correct(x0_measured, obstacles=obs_now)
+
+    prepare(p_pred, w0, obstacles=None, **solve_kw) runs solve_batch(want_duals=True) and keeps (p, w, lam_g, lam_x, obstacles, status); it
+    returns the solve's dict.  correct(x0_measured, xs=None, obstacles=None) takes dp = [x0_measured - x0_pred; xs - xs_pred] and
+    dobs = obstacles - obstacles_pred (a missing argument: unchanged) through one sens_update_batch launch and returns
+    dict(w, u0, step, alpha, info, corrected): step [B] is 1 where alpha == 1 and tau * alpha elsewhere, w = w_pred + step * dw where the solve's
+    status and the update's verdict are both 0 and the prepared plan unchanged elsewhere (corrected [B] bool False; their count is
+    .last['uncorrected']), u0 [B, n_u] the first control of w.  The controller changes no solver state and may be corrected any number of times
+    per prepare."""
+
+    def __init__(self, solver: NmpcSolver, tau: float = 0.99):
+        if not solver.duals_supported():
+            raise RuntimeError("AdvancedStepController needs a handle that returns multipliers (the column-per-lane kernel): this one is pinned to kernel 1 or 2")
+        if not 0.0 < tau <= 1.0:
+            raise ValueError(f"tau must lie in (0, 1], got {tau!r}")
+        self.solver = solver
+        self.tau = float(tau)
+        self.last = {}
+        self._plan = None
+
+    def prepare(self, p_pred, w0, obstacles=None, **solve_kw):
+        s = self.solver
+        torch = s.torch
+        p = s._dev(p_pred, (-1, s.n_p))
+        obs = None if obstacles is None else torch.as_tensor(obstacles, dtype=torch.float64, device=s.device)
+        r = s.solve_batch(p, w0, obstacles=obs, want_duals=True, **solve_kw)
+        self._plan = dict(p=p, w=r["x"], lam_g=r["lam_g"], lam_x=r["lam_x"], obstacles=obs, status=r["status"])
+        self.last = dict(status=r["status"], iters=r["iters"], kkt=r["kkt"], f=r["f"])
+        return r
+
+    def correct(self, x0_measured, xs=None, obstacles=None):
+        if self._plan is None:
+            raise RuntimeError("correct() needs a prepared plan: call prepare() first")
+        s, pl = self.solver, self._plan
+        torch = s.torch
+        nx, nu, N = s.cfg.nx, s.cfg.nu, s.cfg.N
+        B = pl["p"].shape[0]
+        dp = torch.zeros_like(pl["p"])
+        dp[:, :nx] = s._dev(x0_measured, (B, nx)) - pl["p"][:, :nx]
+        if xs is not None:
+            dp[:, nx:] = s._dev(xs, (B, nx)) - pl["p"][:, nx:]
+        dobs = None
+        if obstacles is not None:
+            if pl["obstacles"] is None:
+                raise ValueError("obstacles= needs a plan prepared with obstacles=: the config's own field is not a per-instance parameter")
+            dobs = torch.as_tensor(obstacles, dtype=torch.float64, device=s.device).reshape(pl["obstacles"].shape) - pl["obstacles"]
+        out = s.sens_update_batch(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"])
+        alpha, info = out["alpha"], out["info"]
+        step = torch.where(alpha == 1.0, alpha, self.tau * alpha)
+        ok = (pl["status"] == 0) & (info == 0)
+        w = torch.where(ok[:, None], pl["w"] + step[:, None] * out["dw"], pl["w"])
+        self.last["info"] = info
+        self.last["uncorrected"] = int((~ok).sum())
+        uo = (N + 1) * nx
+        return dict(w=w, u0=w[:, uo: uo + nu], step=step, alpha=alpha, info=info, corrected=ok)

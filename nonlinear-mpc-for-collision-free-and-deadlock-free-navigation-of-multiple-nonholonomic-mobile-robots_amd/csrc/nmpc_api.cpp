@@ -462,6 +462,23 @@ int32_t nmpc_sens_adjoint_batch(nmpc_handle_t *h, int32_t B, const double *p, co
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 
+int32_t nmpc_sens_update_batch(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                               const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw, double *alpha, int32_t *info,
+                               void *stream)
+{
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    if (rc != NMPC_OK) return rc;
+    if (dobs && !obs) return NMPC_E_ARG;      // the handle's own field is no per-instance parameter: it has no change to give
+    if (B == 0) return NMPC_OK;
+    if (!p || !w || !lam_g || !lam_x || !info) return NMPC_E_ARG;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    nmpc::KParams P = h->P;
+    if (obs) set_field(&P, h->cfg, obs, obs_stages);
+    hipError_t e = nmpc::launch_sens_fwd(P, h->cfg.m, B, w, lam_g, lam_x, dp, dobs, rhs, dw, alpha, obs_stages, info, h->ws, (hipStream_t)stream, obs != nullptr);
+    return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
 /* ---- the *_ref entry points: a pose reference per instance, one row or one per stage, in place of the xs half of p */
 int32_t nmpc_eval_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *ref, int32_t ref_stages, const double *obs,
                             int32_t obs_stages, double *f, double *g, void *stream)

@@ -107,6 +107,10 @@ hipError_t launch_sens(const KParams &P, int m, int B, const double *w, const do
 // obsbar [B][obs_stages][K][3], each or both nullptr (obsbar only with ofield); info and ws as launch_sens
 hipError_t launch_sens_adjoint(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *wbar, double *pbar,
                                double *obsbar, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
+// the forward plan update (include/nmpc.h, nmpc_sens_update_batch; nmpc_sens_fwd.hip): dw [B][nvar] and alpha [B], each or both nullptr, for
+// dp [B][2 nx], dobs [B][obs_stages][K][3] (only with ofield) and rhs [B][nvar], each nullptr for zero; info and ws as launch_sens
+hipError_t launch_sens_fwd(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *dp, const double *dobs,
+                           const double *rhs, double *dw, double *alpha, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);
 hipError_t launch_odometry(long n, const double *odom, const double *init, double *pose, int wrap, hipStream_t st);

@@ -361,6 +361,39 @@ class NmpcSolver:
             obsbar = obsbar.reshape(B, len(self.cfg.obstacles), 3)
         return dict(pbar=pbar, obsbar=obsbar, info=info)
 
+    def sens_update_batch(self, p, w, lam_g, lam_x, dp=None, dobs=None, rhs=None, obstacles=None, want_alpha: bool = True):
+        """The forward plan update of (w, lam_g, lam_x) for B instances on the device (nmpc_sens_update_batch), one launch: dw [B, n_var], the
+        first-order change of the plan for dp [B, n_p] = [dx0; dxs], a change dobs of the per-instance obstacle field (the shape of `obstacles`,
+        [B, K, 3] or [B, N, K, 3]) and a general linear term rhs [B, n_var], each None for zero; and alpha [B], the largest step in (0, 1] along
+        (dw, dobs) that keeps every linearised slack non-negative (1.0 exactly when nothing limits it; None with want_alpha=False, dw keeps its
+        bits).  By the linearisation sens_batch uses; obstacles as in solve_batch, and dobs needs it (the config's own field is no per-instance
+        parameter).  Returns dict(dw, alpha, info): info [B] int32 as in sens_batch; an instance with info != 0 gets dw = 0 and alpha = 0.
+        Nothing is clipped: w + step * dw with step <= alpha is the caller's (nmpc_amd.AdvancedStepController).
+        Needs a handle that returns multipliers (duals_supported())."""
+        torch = self.torch
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
+        if dobs is not None and ob is None:
+            raise ValueError("dobs needs obstacles=: the config's own field is not a per-instance parameter")
+        dp = self._dev(dp, (B, self.n_p)) if dp is not None else None
+        rhs = self._dev(rhs, (B, self.n_var)) if rhs is not None else None
+        if dobs is not None:
+            if tuple(getattr(dobs, "shape", np.shape(dobs))) != tuple(getattr(obstacles, "shape", np.shape(obstacles))):
+                raise ValueError("dobs must have the shape of obstacles")
+            dobs = self._dev(dobs, tuple(ob[0].shape))
+        dw = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
+        alpha = torch.empty(B, dtype=torch.float64, device=self.device) if want_alpha else None
+        info = torch.empty(B, dtype=torch.int32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nmpc_sens_update_batch(self._h, B, p.data_ptr(), ptr(ob[0]) if ob is not None else None, ob[1] if ob is not None else 0,
+                                                       w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), ptr(dp), ptr(dobs), ptr(rhs), dw.data_ptr(), ptr(alpha),
+                                                       info.data_ptr(), self._stream()), "nmpc_sens_update_batch")
+        return dict(dw=dw, alpha=alpha, info=info)
+
     def shift_batch(self, p, w, plant: bool = True):
         """device warm-start shift (C6:160-169,460-465) and, if plant, x0 + T f(x0,u0) (casadi_test.py:17-26)."""
         torch = self.torch
