@@ -366,6 +366,39 @@ int32_t nmpc_sens_update_batch(nmpc_handle_t *h, int32_t B, const double *p, con
                                void *stream);
 
 /*
+ * Forward plan update with its multiplier updates: nmpc_sens_update_batch, followed on the same stream by the dlam that go with its dw — the
+ * corrected plan w + a dw keeps multipliers lam + a dlam, so nmpc_kkt_batch can certify it at the moved parameters (stationarity of second
+ * order in the move), and nmpc_sens_* can linearise again at the corrected point without a re-solve.
+ *
+ * Notation as above: grad_lag = grad f + J' lam_g + lam_x as in nmpc_kkt_batch, H the exact Lagrangian Hessian, Sigma_i = max(-lam_g,i, 0) / s_i,
+ * beta_j the bound term on W's diagonal, c the linear term of nmpc_sens_update_batch.  (dw, dlam_g, dlam_x) solve the linearised barrier KKT
+ * system at fixed complementarity products:
+ *   (a) stationarity:   H dw + J' dlam_g + dlam_x + (d_p grad_lag) dp + (d_obs grad_lag) dobs - rhs = 0, with (d_p grad_lag) dp = -2 Q dxs on every
+ *                       X_k, k < N, and (d_obs grad_lag) dobs = sum_i lam_g,i d_o grad g_i dobs over the obstacle rows of stages 1..N-1;
+ *   (b) equality rows:  dX_0 = dx0 and the linearised defects — the dw of nmpc_sens_update_batch;
+ *   (c) inequality rows of stages 1..N-1:  dlam_g,i = Sigma_i ds_i with the ds_i of alpha's items (pair row: 2 e' (dxy_i - dxy_a); obstacle row:
+ *                       n' (dxy - doxy) - dr, that stage's entry of dobs); exactly 0.0 on the rows of stage 0, on the pad rows and where lam_g,i >= 0;
+ *   (d) bounds:         dlam_x,j = beta_j dw_j on X_1..X_N and U; exactly 0.0 on X_0, on an unbounded heading and where lam_x,j == 0;
+ *   (e) initial block and defect rows: the multipliers of the QP's equalities, the unique values with which (a) holds on the rows of X.  With
+ *                       the defect row g_k = X_{k+1} - (X_k + T f) and r = W dw + c:  dnu_{N-1} = -r_XN,  dnu_{k-1} = A_k' dnu_k - r_Xk,
+ *                       dnu_init = A_0' dnu_0 - r_X0.
+ *   dlam_g     [B][n_g]    (c) and (e)
+ *   dlam_x     [B][n_var]  (d)
+ *   alpha_dual [B]         the largest a in (0, 1] that keeps every multiplier's sign: min(1, min_i z_i / (-dz_i)) over the items with z_i > 0 and
+ *                          dz_i < 0 — the inequality rows of (c) with z = -lam_g, dz = -dlam_g, and the bounds of (d) with z = |lam_x|,
+ *                          dz = sign(lam_x) dlam_x.  1.0 exactly when nothing limits it.
+ * With verdict 1 or 2 the instance's dlam_g and dlam_x are zeros and alpha_dual = 0 (dw = 0 and alpha = 0 as above).  The multiplier of p is not
+ * updated here.
+ * dlam_g, dlam_x and alpha_dual may each be NULL; dw, alpha and info are bit for bit those of nmpc_sens_update_batch on the same inputs (with all
+ * three NULL this is that call), and every output keeps its bits when any of the others is left out.  The argument errors and handle rules are
+ * those of nmpc_sens_update_batch.  nmpc_workspace_bytes does not change: the multipliers need no workspace; only a call that asks for them with
+ * dw == NULL makes the handle keep a [max_batch][n_var] buffer of its own for dw from then on (NMPC_E_NOMEM when that fails).
+ */
+int32_t nmpc_sens_update_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w,
+                                     const double *lam_g, const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw,
+                                     double *alpha, double *dlam_g, double *dlam_x, double *alpha_dual, int32_t *info, void *stream);
+
+/*
  * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and
  * nmpc_kkt_batch with the pose reference of every instance given apart from p, one row for the horizon or one per stage (the tutorial
  * lineage of the scripts carries it as P = [x0; x_ref,1 .. x_ref,N]; AS/mpc_control_trajectory_tracking.py tracks a path on its SLSQP route):

@@ -20,7 +20,15 @@ class AdvancedStepController:
     dict(w, u0, step, alpha, info, corrected): step [B] is 1 where alpha == 1 and tau * alpha elsewhere, w = w_pred + step * dw where the solve's
     status and the update's verdict are both 0 and the prepared plan unchanged elsewhere (corrected [B] bool False; their count is
     .last['uncorrected']), u0 [B, n_u] the first control of w.  The controller changes no solver state and may be corrected any number of times
-    per prepare."""
+    per prepare.
+
+    correct(..., update_duals=True) runs nmpc_sens_update_batch_duals: the multipliers move with the plan, so the corrected point can be
+    certified (kkt_batch at the moved parameters) or linearised again (sens_*).  The step is then the smaller of the primal one and
+    1 where alpha_dual == 1, tau * alpha_dual elsewhere — no multiplier changes sign either — and the dict gains lam_g, lam_x (moved by the
+    same step; the prepared ones where corrected is False) and alpha_dual.
+    correct(..., commit=True) implies update_duals and makes the corrected point the controller's base on the corrected instances:
+    (p + step dp, obstacles + step dobs, w, lam_g, lam_x) replace the prepared ones there, the next correct() linearises at them and takes its
+    dp and dobs relative to them; the other instances keep their base.  With both flags off nothing changes."""
 
     def __init__(self, solver: NmpcSolver, tau: float = 0.99):
         if not solver.duals_supported():
@@ -42,13 +50,14 @@ class AdvancedStepController:
         self.last = dict(status=r["status"], iters=r["iters"], kkt=r["kkt"], f=r["f"])
         return r
 
-    def correct(self, x0_measured, xs=None, obstacles=None):
+    def correct(self, x0_measured, xs=None, obstacles=None, update_duals: bool = False, commit: bool = False):
         if self._plan is None:
             raise RuntimeError("correct() needs a prepared plan: call prepare() first")
         s, pl = self.solver, self._plan
         torch = s.torch
         nx, nu, N = s.cfg.nx, s.cfg.nu, s.cfg.N
         B = pl["p"].shape[0]
+        duals = update_duals or commit
         dp = torch.zeros_like(pl["p"])
         dp[:, :nx] = s._dev(x0_measured, (B, nx)) - pl["p"][:, :nx]
         if xs is not None:
@@ -58,12 +67,27 @@ class AdvancedStepController:
             if pl["obstacles"] is None:
                 raise ValueError("obstacles= needs a plan prepared with obstacles=: the config's own field is not a per-instance parameter")
             dobs = torch.as_tensor(obstacles, dtype=torch.float64, device=s.device).reshape(pl["obstacles"].shape) - pl["obstacles"]
-        out = s.sens_update_batch(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"])
+        out = s.sens_update_batch(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"], want_duals=duals)
         alpha, info = out["alpha"], out["info"]
         step = torch.where(alpha == 1.0, alpha, self.tau * alpha)
+        if duals:
+            ad = out["alpha_dual"]
+            step = torch.minimum(step, torch.where(ad == 1.0, ad, self.tau * ad))
         ok = (pl["status"] == 0) & (info == 0)
         w = torch.where(ok[:, None], pl["w"] + step[:, None] * out["dw"], pl["w"])
         self.last["info"] = info
         self.last["uncorrected"] = int((~ok).sum())
         uo = (N + 1) * nx
-        return dict(w=w, u0=w[:, uo: uo + nu], step=step, alpha=alpha, info=info, corrected=ok)
+        res = dict(w=w, u0=w[:, uo: uo + nu], step=step, alpha=alpha, info=info, corrected=ok)
+        if duals:
+            res["lam_g"] = torch.where(ok[:, None], pl["lam_g"] + step[:, None] * out["dlam_g"], pl["lam_g"])
+            res["lam_x"] = torch.where(ok[:, None], pl["lam_x"] + step[:, None] * out["dlam_x"], pl["lam_x"])
+            res["alpha_dual"] = out["alpha_dual"]
+        if commit:
+            obs = pl["obstacles"]
+            if dobs is not None:
+                okf = ok.reshape((B,) + (1,) * (obs.dim() - 1))
+                obs = torch.where(okf, obs + step.reshape(okf.shape) * dobs, obs)
+            self._plan = dict(p=torch.where(ok[:, None], pl["p"] + step[:, None] * dp, pl["p"]), w=w, lam_g=res["lam_g"], lam_x=res["lam_x"],
+                              obstacles=obs, status=pl["status"])
+        return res

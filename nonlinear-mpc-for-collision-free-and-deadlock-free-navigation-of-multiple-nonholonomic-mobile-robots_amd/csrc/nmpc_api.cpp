@@ -38,6 +38,7 @@ struct nmpc_handle {
     int32_t *ord_chk;    // [max_batch + 1] permutation check of a dispatch-order hint: counts, then the "bad" flag
     int32_t *it_buf;     // [max_batch] iteration counts of nmpc_step_batch when the caller passes iters == NULL
     int32_t *st_buf;     // [max_batch] statuses of nmpc_step_batch when the caller passes status == NULL (the in-place update skips failed instances)
+    double *dw_buf;      // [max_batch][n_var] the dw that nmpc_sens_update_batch_duals computes its multipliers from when the caller passes dw == NULL; allocated by the first such call
 };
 
 // makes the handle's device current for one call and restores the caller's on return
@@ -241,6 +242,7 @@ int32_t nmpc_destroy(nmpc_handle_t *h)
     if (h->ord_chk) (void)hipFree(h->ord_chk);
     if (h->it_buf) (void)hipFree(h->it_buf);
     if (h->st_buf) (void)hipFree(h->st_buf);
+    if (h->dw_buf) (void)hipFree(h->dw_buf);
     free(h);
     return NMPC_OK;
 }
@@ -476,6 +478,31 @@ int32_t nmpc_sens_update_batch(nmpc_handle_t *h, int32_t B, const double *p, con
     nmpc::KParams P = h->P;
     if (obs) set_field(&P, h->cfg, obs, obs_stages);
     hipError_t e = nmpc::launch_sens_fwd(P, h->cfg.m, B, w, lam_g, lam_x, dp, dobs, rhs, dw, alpha, obs_stages, info, h->ws, (hipStream_t)stream, obs != nullptr);
+    return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+int32_t nmpc_sens_update_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w, const double *lam_g,
+                                     const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw, double *alpha,
+                                     double *dlam_g, double *dlam_x, double *alpha_dual, int32_t *info, void *stream)
+{
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    if (rc != NMPC_OK) return rc;
+    if (dobs && !obs) return NMPC_E_ARG;
+    if (B == 0) return NMPC_OK;
+    if (!p || !w || !lam_g || !lam_x || !info) return NMPC_E_ARG;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    const bool duals = dlam_g || dlam_x || alpha_dual;
+    if (duals && !dw) {      // the multipliers follow from dw: it goes to the handle's own buffer, which the caller never sees
+        if (!h->dw_buf && hipMalloc((void **)&h->dw_buf, sizeof(double) * (size_t)h->max_batch * (size_t)h->P.nvar) != hipSuccess) return NMPC_E_NOMEM;
+        dw = h->dw_buf;
+    }
+    nmpc::KParams P = h->P;
+    if (obs) set_field(&P, h->cfg, obs, obs_stages);
+    // the update kernel exactly as nmpc_sens_update_batch launches it, then the multipliers from its dw and verdicts on the same stream
+    hipError_t e = nmpc::launch_sens_fwd(P, h->cfg.m, B, w, lam_g, lam_x, dp, dobs, rhs, dw, alpha, obs_stages, info, h->ws, (hipStream_t)stream, obs != nullptr);
+    if (e == hipSuccess && duals)
+        e = nmpc::launch_sens_dual(P, h->cfg.m, B, w, lam_g, lam_x, dp, dobs, rhs, dw, obs_stages, info, dlam_g, dlam_x, alpha_dual, (hipStream_t)stream, obs != nullptr);
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 

@@ -9,6 +9,8 @@
 // row and multiplier indexing of kkt_residual_kernel (nmpc_kernels.hip); the obstacle entry of stage k comes through ObsField.
 // [G_k | g_k] of every stage goes to the pivot-row region [N][KTS] of the handle's workspace (WsLayout, nmpc_solve_common.h), which is idle
 // between the handle's calls and which every solve writes before it reads; the forward pass reads it back.  No solve kernel is involved.
+// The terms of W_k are stated again in nmpc_sens_adj.hip, nmpc_sens_fwd.hip and, as a matrix-vector product, in nmpc_sens_dual.hip: a change to a
+// term of W_k belongs in all four.
 #include "nmpc_solve_common.h"
 
 namespace nmpc {

@@ -8,8 +8,9 @@
 // and eliminated in registers, [P_{k+1} | p_{k+1}] stays in LDS between stages, [G_k | g_k] of every stage goes to the pivot-row region [N][KTS]
 // of the handle's workspace between the two passes.  The assembly of [B A]' P [B A] + W_k and the elimination are RESTATED from nmpc_sens.hip,
 // not shared with it: with the body in one inlined function both kernels computed the parent's bits, but sens_kernel's generated code moved and
-// its call ran 7 % slower, so that kernel stays as it is.  A change to the terms of W_k belongs in both files; the parity
-// tables of the two kernels (tests/sens_points.py) hold each against its own numpy reference.
+// its call ran 7 % slower, so that kernel stays as it is.  A change to the terms of W_k belongs in both files — and in
+// nmpc_sens_fwd.hip and nmpc_sens_dual.hip, which state them again: a change to a term of W_k belongs in all four; the parity tables of the
+// kernels (tests/sens_points.py) hold each against its own numpy reference.
 // Sums over robots that share an obstacle and over stages that share an entry run in a fixed order inside the wavefront — no atomics, the same
 // inputs give the same bits.
 #include "nmpc_solve_common.h"

@@ -9,7 +9,9 @@
 // goes to the pivot-row region [N][KTS] of the handle's workspace between the two passes.  The assembly of [B A]' P [B A] + W_k and the
 // elimination are RESTATED from nmpc_sens.hip — this is the THIRD copy, after nmpc_sens_adj.hip: sharing the body moved sens_kernel's
 // generated code and its call ran 7 % slower, so the other two files stay as they are.  A change to a term of W_k belongs
-// in all three files; the parity tables (tests/sens_points.py) hold each kernel against its own numpy reference.
+// in all four — the three copies and nmpc_sens_dual.hip, which forms W_k dw from the same terms for the multiplier updates that follow this kernel
+// (nmpc_sens_update_batch_duals) and forms c in the order used here; the parity tables (tests/sens_points.py) hold each kernel against its own
+// numpy reference.
 // The terms of c at one entry are added in a fixed order — goal, rhs, then the obstacles in index order — and alpha is one wave-wide minimum:
 // no atomics, the same inputs give the same bits.
 #include "nmpc_solve_common.h"

@@ -361,7 +361,7 @@ class NmpcSolver:
             obsbar = obsbar.reshape(B, len(self.cfg.obstacles), 3)
         return dict(pbar=pbar, obsbar=obsbar, info=info)
 
-    def sens_update_batch(self, p, w, lam_g, lam_x, dp=None, dobs=None, rhs=None, obstacles=None, want_alpha: bool = True):
+    def sens_update_batch(self, p, w, lam_g, lam_x, dp=None, dobs=None, rhs=None, obstacles=None, want_alpha: bool = True, want_duals: bool = False):
         """The forward plan update of (w, lam_g, lam_x) for B instances on the device (nmpc_sens_update_batch), one launch: dw [B, n_var], the
         first-order change of the plan for dp [B, n_p] = [dx0; dxs], a change dobs of the per-instance obstacle field (the shape of `obstacles`,
         [B, K, 3] or [B, N, K, 3]) and a general linear term rhs [B, n_var], each None for zero; and alpha [B], the largest step in (0, 1] along
@@ -369,6 +369,10 @@ class NmpcSolver:
         bits).  By the linearisation sens_batch uses; obstacles as in solve_batch, and dobs needs it (the config's own field is no per-instance
         parameter).  Returns dict(dw, alpha, info): info [B] int32 as in sens_batch; an instance with info != 0 gets dw = 0 and alpha = 0.
         Nothing is clipped: w + step * dw with step <= alpha is the caller's (nmpc_amd.AdvancedStepController).
+        want_duals=True (nmpc_sens_update_batch_duals: the same launch, then one more on its stream) adds the multiplier updates that go with dw,
+        dlam_g [B, n_g] and dlam_x [B, n_var], and alpha_dual [B], the largest step in (0, 1] that keeps every multiplier's sign: (w + a dw,
+        lam_g + a dlam_g, lam_x + a dlam_x) is a primal-dual point at the moved parameters, for kkt_batch and for the sens_* calls.  dw, alpha and
+        info keep their bits; zeros and alpha_dual = 0 where info != 0.
         Needs a handle that returns multipliers (duals_supported())."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
@@ -388,6 +392,16 @@ class NmpcSolver:
         alpha = torch.empty(B, dtype=torch.float64, device=self.device) if want_alpha else None
         info = torch.empty(B, dtype=torch.int32, device=self.device)
         ptr = lambda t: t.data_ptr() if t is not None else None
+        if want_duals:
+            dlam_g = torch.empty((B, self.n_g), dtype=torch.float64, device=self.device)
+            dlam_x = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
+            alpha_dual = torch.empty(B, dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.nmpc_sens_update_batch_duals(self._h, B, p.data_ptr(), ptr(ob[0]) if ob is not None else None, ob[1] if ob is not None else 0,
+                                                                 w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), ptr(dp), ptr(dobs), ptr(rhs), dw.data_ptr(),
+                                                                 ptr(alpha), dlam_g.data_ptr(), dlam_x.data_ptr(), alpha_dual.data_ptr(), info.data_ptr(),
+                                                                 self._stream()), "nmpc_sens_update_batch_duals")
+            return dict(dw=dw, alpha=alpha, info=info, dlam_g=dlam_g, dlam_x=dlam_x, alpha_dual=alpha_dual)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.nmpc_sens_update_batch(self._h, B, p.data_ptr(), ptr(ob[0]) if ob is not None else None, ob[1] if ob is not None else 0,
                                                        w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), ptr(dp), ptr(dobs), ptr(rhs), dw.data_ptr(), ptr(alpha),

@@ -4,7 +4,7 @@
 The batch is solved once with want_duals=True; then, inside every repetition, the plain solve launch, the sensitivity call on that solve's
 own output in its four shapes (gains of stage 0 / of every stage, with and without dw) and the adjoint call (nmpc_sens_adjoint_batch, pbar)
 alternate, each launch timed with HIP events on the launch stream; so do the forward plan update (nmpc_sens_update_batch: dp alone with and
-without alpha) and its yardstick, nmpc_sens_batch(dp, gains=None).  The adjoint's obstacle cotangent needs a per-instance field: a second
+without alpha, and with the multiplier updates of nmpc_sens_update_batch_duals behind it) and its yardstick, nmpc_sens_batch(dp, gains=None).  The adjoint's obstacle cotangent needs a per-instance field: a second
 handle (six robots, eight obstacles, N = 20, the config's field given per instance) is solved the same way and its plain solve, the
 forward call, the adjoint and the update (dp and dobs) with a static ([B, K, 3]) and a per-stage ([B, N, K, 3]) field alternate in the same
 repetitions.
@@ -51,6 +51,7 @@ def main():
     variants["dw_only"] = sens(None, True)      # the yardstick of the update: the same dw from nmpc_sens_batch
     variants["update"] = lambda: s.sens_update_batch(dP, r["x"], r["lam_g"], r["lam_x"], dp=dp)
     variants["update_no_alpha"] = lambda: s.sens_update_batch(dP, r["x"], r["lam_g"], r["lam_x"], dp=dp, want_alpha=False)
+    variants["update_duals"] = lambda: s.sens_update_batch(dP, r["x"], r["lam_g"], r["lam_x"], dp=dp, want_duals=True)
     # the obstacle cotangent: six robots among eight obstacles, every instance holding the config's field, static and per stage
     ocfg = nmpc_amd.six_robots_eight_obstacles(N=cfg.N, obstacles=bench.make_batch("composite", 0, 1)[0].obstacles)
     ocfg.max_iter = cfg.max_iter
@@ -74,11 +75,14 @@ def main():
     variants["obs_dw_only"] = lambda: so.sens_batch(dPo, ro["x"], ro["lam_g"], ro["lam_x"], dp=dpo, obstacles=f1)
     variants["obs_update_static"] = lambda: so.sens_update_batch(dPo, ro["x"], ro["lam_g"], ro["lam_x"], dp=dpo, dobs=dob1, obstacles=f1)
     variants["obs_update_moving"] = lambda: so.sens_update_batch(dPo, ro["x"], ro["lam_g"], ro["lam_x"], dp=dpo, dobs=dobN, obstacles=fN)
+    variants["obs_update_moving_duals"] = lambda: so.sens_update_batch(dPo, ro["x"], ro["lam_g"], ro["lam_x"], dp=dpo, dobs=dobN, obstacles=fN, want_duals=True)
     res = {v: timed(f)[1] for v, f in variants.items()}      # warm-up (code objects, allocator)
     assert all(torch.equal(res["plain_solve"][k], r[k]) for k in ("x", "f", "status", "iters", "kkt"))      # the calls in between leave the solve as it was
     assert torch.equal(res["gains1"]["gains"][:, 0], res["gainsN_dw"]["gains"][:, 0]) and torch.equal(res["gains1_dw"]["dw"], res["gainsN_dw"]["dw"])
     assert torch.equal(res["adjoint"]["info"], res["gainsN_dw"]["info"]) and torch.equal(res["obs_adjoint_static"]["pbar"], res["obs_adjoint_moving"]["pbar"])
     assert torch.equal(res["update"]["info"], res["dw_only"]["info"]) and torch.equal(res["update"]["dw"], res["update_no_alpha"]["dw"])
+    assert torch.equal(res["update_duals"]["dw"], res["update"]["dw"]) and torch.equal(res["update_duals"]["alpha"], res["update"]["alpha"])
+    assert torch.equal(res["obs_update_moving_duals"]["dw"], res["obs_update_moving"]["dw"])
     assert torch.allclose(res["update"]["dw"], res["dw_only"]["dw"], rtol=0.0, atol=1e-9 * float(res["dw_only"]["dw"].abs().max()))
     ms = {v: [] for v in variants}
     for _ in range(reps):
@@ -94,9 +98,10 @@ def main():
         base = float(np.median(ms["obs_plain_solve" if v.startswith("obs_") else "plain_solve"]))      # each call against the solve that feeds it
         out[v] = {"ms_median": float(np.median(t)), "ms_min": float(np.min(t)), "ms_max": float(np.max(t)), "vs_plain_solve": float(np.median(t)) / base}
     print("six robots B=%d: " % B + ", ".join("%s %.3f ms [%.3f, %.3f]" % (v, out[v]["ms_median"], out[v]["ms_min"], out[v]["ms_max"]) for v in variants)
-          + "; gains S=N + dw at %.1f %%, adjoint at %.1f %% of the plain solve launch, adjoint with obsbar (per stage) at %.1f %% of its own; update (dp) at %.2f x nmpc_sens_batch(dp, gains=None), update (dp, dobs per stage) at %.2f x; info %s" % (
+          + "; gains S=N + dw at %.1f %%, adjoint at %.1f %% of the plain solve launch, adjoint with obsbar (per stage) at %.1f %% of its own; update (dp) at %.2f x nmpc_sens_batch(dp, gains=None), update (dp, dobs per stage) at %.2f x; update with multipliers at %.2f x the plain update, among obstacles %.2f x; info %s" % (
               100.0 * out["gainsN_dw"]["vs_plain_solve"], 100.0 * out["adjoint"]["vs_plain_solve"], 100.0 * out["obs_adjoint_moving"]["vs_plain_solve"],
-              out["update"]["ms_median"] / out["dw_only"]["ms_median"], out["obs_update_moving"]["ms_median"] / out["obs_dw_only"]["ms_median"], out["info_counts"]),
+              out["update"]["ms_median"] / out["dw_only"]["ms_median"], out["obs_update_moving"]["ms_median"] / out["obs_dw_only"]["ms_median"], out["update_duals"]["ms_median"] / out["update"]["ms_median"],
+              out["obs_update_moving_duals"]["ms_median"] / out["obs_update_moving"]["ms_median"], out["info_counts"]),
           file=sys.stderr, flush=True)
     print(json.dumps(out), flush=True)
 
