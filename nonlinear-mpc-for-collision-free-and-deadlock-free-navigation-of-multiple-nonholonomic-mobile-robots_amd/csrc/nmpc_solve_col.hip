@@ -59,6 +59,12 @@ __device__ __forceinline__ double lane_read(double v, int lane)      // uniform 
 #ifndef NMPC_COL_RP
 #define NMPC_COL_RP 1        // row-paired backward sweep for two to six robots (see the sweep); 0 keeps one row per register (A/B)
 #endif
+#ifndef NMPC_COL_RP_GATHER
+#define NMPC_COL_RP_GATHER 3 // how the row-paired pivot step replicates its pivot row: 0 lane swaps (A/B); 1 `ur` by lane gather, `own` by swap; 2 both by gather, at their own pivot; 3 both by gather, requested one pivot ahead (docs/PIVOT_GATHER.md)
+#endif
+#ifndef NMPC_COL_RP_GATHER_FROM
+#define NMPC_COL_RP_GATHER_FROM 5 // smallest team that gathers: five and six robots eliminate 15 registers per pivot, which the gathers fly under; two robots (5 registers) measured 0.7 % slower with them, three and four (10) are not measured and keep the swaps
+#endif
 
 // lane that owns column c of the augmented matrix: state column NU + s on lane s, control column a on lane NX + a
 #define LC(c) (((c) < NU) ? NX + (c) : (c) - NU)
@@ -838,6 +844,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             const bool needxy = (c_state && cd == 2) || (c_ctrl && cd == 0), needth = c_ctrl && cd == 1;
             const int srcA2 = 4 * (needxy ? lb + NC + 3 * cp : (needth ? lb + NC + 3 * cp + 2 : tid));
             const int srcB2 = 4 * (needxy ? lb + NC + 3 * cp + 1 : (needth ? lb + NC + 3 * cp + 2 : tid));
+            // byte addresses of the pivot step's two lane gathers (step 5): lane l reads lane l & 31, and lane 16 (l >> 5) + (l & 15), of the pivot row's half
+            [[maybe_unused]] const int gown = 4 * (tid & 31), gur = 4 * (16 * (tid >> 5) + (tid & 15));
             // ---- terminal cost-to-go P_N = diag(hd_N), p_N = g_N — or, resuming after a rejected pivot, the cost-to-go saved on entry to stage kst
             double m[RR + 1];
             static_for<0, NC>([&](auto rc) { m[decltype(rc)::value] = 0.0; });
@@ -956,6 +964,18 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     rcv = rcp_nr(d);
                     return lane_read(rcv, dl);
                 };
+                // The pivot row is replicated twice: own = [P0 P1 | P0 P1] (the row on every lane's own column, in both halves) and
+                // ur = [P0 P0 | P1 P1] (what row_newbcast reads the multipliers from).  Both are fixed lane permutations of m[ij]: two
+                // lane gathers through the LDS crossbar, whose addresses (gown, gur; + 128 bytes for a row of the upper half, the
+                // instruction's offset field) are constants of the sweep, instead of six lane swaps on copies.  m[ij] is not rearranged:
+                // the half that held the pivot row is dead from here on, the other half's row is gathered from its own half at its turn.
+                constexpr int GA = M_ >= NMPC_COL_RP_GATHER_FROM ? NMPC_COL_RP_GATHER : 0;
+                double own_n = 0.0, ur_n = 0.0;          // GA == 3: the replicas of the next pivot row, requested one pivot ahead
+                auto replicate = [&](auto jc) {
+                    constexpr int hj = rp_half(decltype(jc)::value), ij = rp_slot(decltype(jc)::value);
+                    own_n = lane_gather(gown + 128 * hj, m[ij]); ur_n = lane_gather(gur + 128 * hj, m[ij]);
+                };
+                if constexpr (GA == 3) replicate(std::integral_constant<int, 0>{});
                 double inv_cur = pivot_inv(std::integral_constant<int, 0>{});
                 double rhsv = 0.0;
                 static_for<0, NU>([&](auto jc) {
@@ -964,10 +984,16 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     const double rhs_j = lane_read(m[RR], 16 * hj + ij);
                     // the diagonal's lane holds both factors of the row's right-hand side: m[RR] (both halves carry that row) and the reciprocal
                     rhsv = (tid == 48 * hj + ij) ? -m[RR] * rcv : rhsv;
-                    // own = the pivot row on every lane's own column, in both halves.  The swap leaves the OTHER row of the register in
-                    // both halves of m[ij]: the pivot row itself is dead from here on, the other one keeps its place
-                    double own = m[ij];
-                    if constexpr (hj == 0) swap32(own, m[ij]); else swap32(m[ij], own);
+                    double own, ur;
+                    if constexpr (GA == 3) { own = own_n; ur = ur_n; }
+                    else if constexpr (GA == 2) { replicate(jc); own = own_n; ur = ur_n; }
+                    else {
+                        if constexpr (GA == 1) ur = lane_gather(gur + 128 * hj, m[ij]);
+                        // own by a swap, which leaves the OTHER row of the register in both halves of m[ij]: the pivot row itself is
+                        // dead from here on, the other one keeps its place
+                        own = m[ij];
+                        if constexpr (hj == 0) swap32(own, m[ij]); else swap32(m[ij], own);
+                    }
                     const double rjv = own * inv;
                     double nrjv = -rjv;
                     {
@@ -976,14 +1002,19 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                         if constexpr (j == NU - 1) pend_row = (mc > j) ? nrjv : 0.0;
                         else gkrow[j * G::LDC] = (mc > j) ? nrjv : 0.0;
                     }
-                    // ur = [P0 P0 P1 P1] from own = [P0 P1 P0 P1]
-                    double ur = own, ub = own;
-                    swap16(ur, ub);                   // ur = [P0 P0 P0 P0], ub = [P1 P1 P1 P1]
-                    swap32(ur, ub);                   // ur = [P0 P0 P1 P1]
-                    asm("s_nop 1" : "+v"(ur));        // VALU write -> DPP read of the same VGPR: 2 wait states
+                    if constexpr (GA == 0) {
+                        // ur = [P0 P0 P1 P1] from own = [P0 P1 P0 P1]
+                        double ub = own;
+                        ur = own;
+                        swap16(ur, ub);               // ur = [P0 P0 P0 P0], ub = [P1 P1 P1 P1]
+                        swap32(ur, ub);               // ur = [P0 P0 P1 P1]
+                        asm("s_nop 1" : "+v"(ur));    // VALU write -> DPP read of the same VGPR: 2 wait states
+                    }
+                    // (a gathered ur reaches its DPP reads behind the s_waitcnt of the gather, which the compiler places: no VALU write, no s_nop)
                     auto elim = [&](auto ac) { constexpr int i = decltype(ac)::value; fmac_rowb<i>(m[i], ur, nrjv); };
                     if constexpr (j + 1 < NU) {       // the next pivot row first: its reciprocal overlaps the other rows
                         elim(std::integral_constant<int, rp_slot(j + 1)>{});
+                        if constexpr (GA == 3) replicate(std::integral_constant<int, j + 1>{});      // final from here: the gathers fly under the other rows
                         inv_cur = pivot_inv(std::integral_constant<int, j + 1>{});
                     }
                     // a control register stays live while one of its two rows has not been a pivot yet

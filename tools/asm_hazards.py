@@ -5,6 +5,11 @@ allocator inserting no copy between marker and consumer.  This script checks the
 instruction, walk back over 2 wait states (s_nop N counts N + 1, any other instruction 1) and report a VALU / permlane-swap write of
 the DPP source register inside that window.
 
+A DPP source that comes from a lane gather (`ds_bpermute_b32`, any LDS instruction with a result) is not a VALU write and needs no wait
+state, but the read must sit behind the `s_waitcnt lgkmcnt(n)` that covers the gather: LDS results arrive in order, so lgkmcnt(n) leaves
+the last n LDS instructions pending.  The compiler places that wait for the asm's operands; a DPP read of a still-pending register is
+reported as a hazard too.
+
     python tools/asm_hazards.py <kernel.s> [symbol prefix]        -> prints "<n dpp> <n hazards>", exit code 1 on a hazard
 """
 import re
@@ -26,6 +31,7 @@ def check(path, prefix=""):
     hazards = []
     hist = []      # (opcode, set of VGPRs written by a VALU op, wait states the instruction provides)
     infn = False
+    pending = []   # LDS instructions with a result that no s_waitcnt has covered yet, in issue order: sets of VGPRs
     for ln in lines:
         t = ln.split(";")[0].strip()
         if not t or t.startswith("."):
@@ -36,6 +42,7 @@ def check(path, prefix=""):
             if not t.startswith(".L"):
                 infn = t.startswith(prefix)
                 hist = []
+                pending = []
             else:
                 hist.append(("label", set(), 0))
             continue
@@ -47,6 +54,8 @@ def check(path, prefix=""):
         if "_dpp" in op:
             n_dpp += 1
             src = regs(ops[1].split()[0]) if len(ops) > 1 else set()
+            if any(pw & src for pw in pending):
+                hazards.append((op, sorted(src), "LDS result without s_waitcnt", 0))
             ws = 0
             for pop, pw, pws in reversed(hist):
                 if ws >= 2:
@@ -62,6 +71,12 @@ def check(path, prefix=""):
             written = regs(ops[0].split()[0])
             if "permlane" in op and "swap" in op and len(ops) > 1:
                 written |= regs(ops[1].split()[0])
+        if op.startswith("ds_") and ops and regs(ops[0].split()[0]) and not op.startswith(("ds_write", "ds_store")):
+            pending.append(regs(ops[0].split()[0]))
+        if op == "s_waitcnt":
+            mm = re.search(r"lgkmcnt\((\d+)\)", t)
+            if mm:
+                pending = pending[len(pending) - int(mm.group(1)):] if int(mm.group(1)) else []
         wsn = 1
         if op == "s_nop":
             wsn = int(ops[0], 0) + 1

@@ -31,12 +31,40 @@ def rowb(u, n):        # row_newbcast:n — lane n of the executing lane's own r
     return u[(lanes & ~15) + n]
 
 
+def lane_gather(src4, v):      # ds_bpermute_b32: lane l reads lane (src4[l] / 4) mod 64 of v
+    return v[(np.asarray(src4) >> 2) & 63]
+
+
+def gather_addrs():
+    """per-lane byte addresses of the pivot step's two gathers (+ 128 for a pivot row of the upper half): own reads lane l & 31, ur reads
+    lane 16 (l >> 5) + (l & 15) of the pivot row's half"""
+    l = np.arange(64)
+    return 4 * (l & 31), 4 * (16 * (l >> 5) + (l & 15))
+
+
+def replicate_swap(mij, hj):
+    """the pivot row (half hj of register mij) replicated by lane swaps, as the kernel's NMPC_COL_RP_GATHER = 0 does it:
+    (own = [P0 P1 | P0 P1], ur = [P0 P0 | P1 P1], the register as the swaps leave it — the OTHER row in both halves)"""
+    if hj == 0: own, left = swap32(mij, mij)
+    else: left, own = swap32(mij, mij)
+    ur, ub = swap16(own, own); ur, ub = swap32(ur, ub)
+    return own, ur, left
+
+
+def replicate_gather(mij, hj):
+    """the same two replicas by lane gathers from the register itself, which stays as it is"""
+    gown, gur = gather_addrs()
+    return lane_gather(gown + 128 * hj, mij), lane_gather(gur + 128 * hj, mij), mij.copy()
+
+
 def rp_slot(j): return 2 * ((j >> 1) >> 1) + (j & 1)
 def rp_half(j): return (j >> 1) & 1
 def rp_live(i, jj, nc, nu): return i >= nc or (4 * (i >> 1) + (i & 1) > jj) or (4 * (i >> 1) + 2 + (i & 1) > jj and 4 * (i >> 1) + 2 + (i & 1) < nu)
 
 
-def rp_sweep(pk, M_, N, off):
+def rp_sweep(pk, M_, N, off, form=None):
+    """form: None — the replicas taken from the register, which keeps both rows; 'swap' / 'gather' — replicate_swap / replicate_gather, the
+    register left as each leaves it (the kernel's two forms, literally)"""
     NX, NU = 3 * M_, 2 * M_; NZ = NX + NU
     PK_G, PK_HD, PK_HXY, PK_HVT, PK_E, PK_C, PK_CF, PK_ZERO = off
     MP = (M_ + 1) // 2; NC = 2 * MP; NS = 3 * MP; RR = NC + NS
@@ -104,6 +132,8 @@ def rp_sweep(pk, M_, N, off):
             oc, od = swap32(m[ij], m[ij])
             ua, ub = swap16(m[ij], m[ij]); ua, ub = swap32(ua, ub)
             own = od if hj else oc; ur = ub if hj else ua
+            if form is not None:
+                own, ur, m[ij] = (replicate_swap if form == "swap" else replicate_gather)(m[ij], hj)
             for lane in range(32):          # what the lower half stores: the pivot row by natural column index
                 if cvalid[lane]: R_[j, rcol[lane]] = own[lane]
             R_[j, NZ] = rhs_j
