@@ -99,15 +99,16 @@ hipError_t launch_eval(const KParams &P, const PoseRef &xr, int m, int B, const 
 // KKT residuals of (w, lam_g, lam_x): res [B][6] = (stat, eq, ineq, bnd, compl, sign), grad_lag [B][nvar] or nullptr (include/nmpc.h, nmpc_kkt_batch)
 hipError_t launch_kkt(const KParams &P, const PoseRef &xr, int m, int B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res, double *grad_lag,
                       hipStream_t st, bool ofield);
+constexpr int NMPC_SENS_OBS = 16;      // the sensitivity kernels' MS = team size + NMPC_SENS_OBS * (per-instance obstacle field), as eval_kernel's NMPC_EVAL_OBS
 // plan sensitivities of (w, lam_g, lam_x) (include/nmpc.h, nmpc_sens_batch; nmpc_sens.hip): dw [B][nvar] for dp [B][2 nx] (both or neither), gains [B][gain_stages][nu][nx] or
 // nullptr, info [B]; ws: the workspace of a handle that runs on the column kernel (its pivot-row region holds [G_k | g_k] between the two passes)
 hipError_t launch_sens(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *dp, double *dw, double *gains,
                        int gain_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
-// the transposes of the same maps applied to wbar [B][nvar] (include/nmpc.h, nmpc_sens_adjoint_batch; nmpc_sens_adj.hip): pbar [B][2 nx] and
+// the transposes of the same maps applied to wbar [B][nvar] (include/nmpc.h, nmpc_sens_adjoint_batch; nmpc_sens.hip): pbar [B][2 nx] and
 // obsbar [B][obs_stages][K][3], each or both nullptr (obsbar only with ofield); info and ws as launch_sens
 hipError_t launch_sens_adjoint(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *wbar, double *pbar,
                                double *obsbar, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
-// the forward plan update (include/nmpc.h, nmpc_sens_update_batch; nmpc_sens_fwd.hip): dw [B][nvar] and alpha [B], each or both nullptr, for
+// the forward plan update (include/nmpc.h, nmpc_sens_update_batch; nmpc_sens.hip): dw [B][nvar] and alpha [B], each or both nullptr, for
 // dp [B][2 nx], dobs [B][obs_stages][K][3] (only with ofield) and rhs [B][nvar], each nullptr for zero; info and ws as launch_sens
 hipError_t launch_sens_fwd(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *dp, const double *dobs,
                            const double *rhs, double *dw, double *alpha, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);

@@ -1,25 +1,23 @@
 // nmpc_sens_dual.hip — the multiplier updates that go with the forward plan update (include/nmpc.h, nmpc_sens_update_batch_duals): given the dw
-// that sens_fwd_kernel (nmpc_sens_fwd.hip) has written, (dlam_g, dlam_x) complete the solution of the linearised barrier KKT system at fixed
+// that sens_kernel<MS, SENS_UPDATE> (nmpc_sens.hip) has written, (dlam_g, dlam_x) complete the solution of the linearised barrier KKT system at fixed
 // complementarity products, and alpha_dual says how much of them keeps every multiplier's sign.
 //
-// Nothing is eliminated here.  With r = W dw + c (W and c as in nmpc_sens_fwd.hip) stationarity in X_k reads r_Xk + dnu_{k-1} - A_k' dnu_k = 0
+// Nothing is eliminated here.  With r = W dw + c (W and c as in nmpc_sens.hip, SENS_UPDATE) stationarity in X_k reads r_Xk + dnu_{k-1} - A_k' dnu_k = 0
 // for the multipliers dnu_k of the linearised defects X_{k+1} - (X_k + T f), so one backward walk gives them all: dnu_{N-1} = -r_XN,
 // dnu_{k-1} = A_k' dnu_k - r_Xk, dnu_init = A_0' dnu_0 - r_X0.  The X rows of r_k = W_k [dU_k; dX_k] + c_k are formed as a matrix-vector product
-// from the terms of W_k, never as a matrix (the U rows define nothing: r_Uk - B_k' dnu_k = 0 holds by the choice of dU_k): a change to a term of W_k belongs in all four files (nmpc_sens.hip, nmpc_sens_adj.hip, nmpc_sens_fwd.hip and this
-// one); the parity tables (tests/sens_points.py) hold each kernel against its own numpy reference.  The inequality rows get Sigma_i ds_i with the
+// from the terms of W_k, never as a matrix (the U rows define nothing: r_Uk - B_k' dnu_k = 0 holds by the choice of dU_k): a term of W_k lives in two places, nmpc_sens.hip and this
+// file, and a change to one belongs in both; the parity tables (tests/sens_points.py) hold each kernel against its own numpy reference.  The inequality rows get Sigma_i ds_i with the
 // ds of the update's alpha items, the bounds beta_j dw_j.
 //
 // One wavefront per instance: lane j < NZ owns entry j of the stage vector [U_k; X_k], the pair rows of a stage go to lanes j < NP, its obstacle
 // rows through a strided loop (ten robots among eight obstacles have 80).  dnu of the current stage, dX_k, dU_k and the stage's lam_g block live
-// in LDS; no workspace.  The terms of c at one entry are added in sens_fwd_kernel's order, alpha_dual is one wave-wide minimum: no atomics, the
+// in LDS; no workspace.  The terms of c at one entry are added in sens_kernel's order, alpha_dual is one wave-wide minimum: no atomics, the
 // same inputs give the same bits.
 #include "nmpc_solve_common.h"
 
 namespace nmpc {
 
-constexpr int NMPC_SENS_DUAL_OBS = 16;      // MS = team size + NMPC_SENS_DUAL_OBS * (per-instance obstacle field), as sens_kernel's
-
-// S: obs_stages of the call (1 or N; read only with dobs).  info [B] holds the verdicts sens_fwd_kernel wrote on the same stream.
+// MS = team size + NMPC_SENS_OBS * (per-instance obstacle field), as sens_kernel's.  S: obs_stages of the call (1 or N; read only with dobs).  info [B] holds the verdicts sens_kernel<MS, SENS_UPDATE> wrote on the same stream.
 template <int MS>
 __global__ __launch_bounds__(64) void sens_dual_kernel(const KParams P, const double *__restrict__ w, const double *__restrict__ lam_g,
                                                        const double *__restrict__ lam_x, const double *__restrict__ dp, const double *__restrict__ dobs,
@@ -27,7 +25,7 @@ __global__ __launch_bounds__(64) void sens_dual_kernel(const KParams P, const do
                                                        const int32_t *__restrict__ info, double *__restrict__ dlam_g, double *__restrict__ dlam_x,
                                                        double *__restrict__ alpha_dual)
 {
-    constexpr int M_ = MS % NMPC_SENS_DUAL_OBS, OS = MS / NMPC_SENS_DUAL_OBS;
+    constexpr int M_ = MS % NMPC_SENS_OBS, OS = MS / NMPC_SENS_OBS;
     using G = G2<M_, 0>;
     constexpr int NX = G::NX, NU = G::NU, NZ = G::NZ, NP = G::NP;
     static_assert(NZ <= 64, "one lane per entry of the stage vector");
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(64) void sens_dual_kernel(const KParams P, const do
         if (j < NZ) lx[j] = isu ? lxU[(size_t)k * NU + j] : (k > 0 ? lxX[(size_t)k * NX + j - NU] : 0.0);
         for (int e = j; e < P.rowsk; e += 64) lk[e] = lgk[e];
         if (dgk && j < NX) dgk[j] = nu[j];      // dnu_k, from the stage above
-        // ---- the linear term c of the stage in sens_fwd_kernel's order: the goal, then rhs, then (M_o dobs) of the robot's obstacle rows in index order
+        // ---- the linear term c of the stage in sens_kernel's order: the goal, then rhs, then (M_o dobs) of the robot's obstacle rows in index order
         if (j < NX) {
             double q = qgoal;
             if (rhX) q -= rhX[(size_t)k * NX + j];
@@ -209,7 +207,7 @@ template <int M_> static hipError_t launch_sens_dual_m(const KParams &P, int B, 
                                                        double *dlam_x, double *alpha_dual, hipStream_t st, bool ofield)
 {
     if (ofield)
-        hipLaunchKernelGGL((sens_dual_kernel<M_ + NMPC_SENS_DUAL_OBS>), dim3((unsigned)B), dim3(64), 0, st, P, w, lam_g, lam_x, dp, dobs, rhs, dw, S, info, dlam_g,
+        hipLaunchKernelGGL((sens_dual_kernel<M_ + NMPC_SENS_OBS>), dim3((unsigned)B), dim3(64), 0, st, P, w, lam_g, lam_x, dp, dobs, rhs, dw, S, info, dlam_g,
                            dlam_x, alpha_dual);
     else
         hipLaunchKernelGGL((sens_dual_kernel<M_>), dim3((unsigned)B), dim3(64), 0, st, P, w, lam_g, lam_x, dp, dobs, rhs, dw, S, info, dlam_g, dlam_x, alpha_dual);

@@ -1,6 +1,6 @@
-"""-m gpu: nmpc_sens_adjoint_batch (csrc/nmpc_sens_adj.hip) and nmpc_amd.NmpcLayer.
+"""-m gpu: nmpc_sens_adjoint_batch (csrc/nmpc_sens.hip) and nmpc_amd.NmpcLayer.
 
-Every instantiation of sens_adjoint_kernel<MS> against tests/sens_adjoint_ref.py on the constructed points of tests/sens_points.py, with a seeded
+Every instantiation of sens_kernel<MS, SENS_ADJOINT> against tests/sens_adjoint_ref.py on the constructed points of tests/sens_points.py, with a seeded
 cotangent that has weight on every entry: pbar on every row, obsbar on the rows with a per-instance field.  The bound is the project's:
 100 x that point's spread + 1e-12 relative to max|pbar| / max|obsbar|; a kernel without the Sigma n n' term or the radius column, or one that reads
 the wrong entry of the field, is 1000 x that bound away (tests/test_sens_adjoint_host.py).  Then the verdict batches, the bit-level properties,

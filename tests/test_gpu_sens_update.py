@@ -1,6 +1,6 @@
-"""-m gpu: nmpc_sens_update_batch (csrc/nmpc_sens_fwd.hip) and nmpc_amd.AdvancedStepController.
+"""-m gpu: nmpc_sens_update_batch (csrc/nmpc_sens.hip) and nmpc_amd.AdvancedStepController.
 
-Every instantiation of sens_fwd_kernel<MS> against tests/sens_update_ref.py on the constructed points of tests/sens_points.py, with the point's dp
+Every instantiation of sens_kernel<MS, SENS_UPDATE> against tests/sens_update_ref.py on the constructed points of tests/sens_points.py, with the point's dp
 and a seeded dobs and rhs that have weight on every entry: dw and alpha on every row.  The bound is the project's: 100 x that point's spread
 + 1e-12, relative to max|dw| and to alpha; a kernel without the Sigma n n' term or the radius column of M_o, or one that reads the wrong entry
 of the field, is 1000 x that bound away (tests/test_sens_update_host.py).  Then the bit-level properties, the agreement with nmpc_sens_batch and

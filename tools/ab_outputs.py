@@ -1,5 +1,6 @@
 """Development aid (GPU box): bit-identity of two library builds.  One process per library:
     NMPC_SO=<a.so> python tools/ab_outputs.py a.npz          every output array of the fixed case list below, solved on that library
+    NMPC_SO=<a.so> python tools/ab_outputs.py a.npz sens     only the named groups of the list: solve, lidar, sens
     NMPC_SO=<b.so> python tools/ab_outputs.py b.npz
     python tools/ab_outputs.py --compare a.npz b.npz         lists the arrays whose bit patterns differ (exit status 1 if any)
     python tools/ab_outputs.py --compare-dumps dirA dirB     the same for two `bench.py --dump-outputs` directories
@@ -7,7 +8,10 @@ Cases: the ten shapes of tests/test_gpu_phase_passes.py (plain call and with mul
 on every pin (1 .. 5: they walk the barrier restarts, both cold retries and the elastic phase of all three swarm kernels), the moving-obstacle
 rescue fixtures (per-instance field) on pins 3, 4, 5, nmpc_solve_batch_duals on the six-robot bench batch, every kernel-1 and kernel-2 row of
 tests/kernel_variants.TABLE by its own recipe, and the LIDAR kernel: one recipe of tests/lidar_variants.TABLE per instantiation and
-LIDAR_BENCH_PICK of its bench batch.  After each swarm solve the handle's workspace is recorded too, as one sha256 per instance (`<case>/ws`):
+LIDAR_BENCH_PICK of its bench batch; and the sensitivity calls on the constructed points of every row of tests/sens_points.SENS_TABLE (N = 2 .. 12,
+four to six points a row): nmpc_sens_batch (the gains of every stage and dw), nmpc_sens_adjoint_batch (pbar, and obsbar on the rows with a
+per-instance field), nmpc_sens_update_batch (dw, alpha) and nmpc_sens_update_batch_duals, with the seeded cotangent, dobs and rhs of the GPU
+tests and the verdicts of each.  After each swarm solve the handle's workspace is recorded too, as one sha256 per instance (`<case>/ws`):
 a changed scratch value shows even where no output moved.  NaN payloads count: arrays are compared as raw bytes."""
 import ctypes as C
 import hashlib
@@ -101,12 +105,49 @@ def run_lidar(out):
     record(out, "lidar_bench_pick", solver(lc, 2000, len(P)), P, W, ws=False)
 
 
-def run(path):
+def run_sens(out):
+    import nmpc_amd
+    from tests import helpers as Hh
+    from tests import sens_adjoint_ref as AR
+    from tests import sens_points as SP
+    from tests import sens_update_ref as UR
+    stack = lambda xs: None if xs[0] is None else np.stack(xs)
+    for r in SP.SENS_TABLE:
+        pts = SP.points(r); n = len(pts)
+        s = nmpc_amd.NmpcSolver(Hh.to_product_cfg(r.cfg, max_iter=10, pair_rows=r.cfg.pair_rows), max_batch=2 * n + 2)      # the handle of the GPU tests
+        a = [np.stack([getattr(pt, k) for pt in pts]) for k in ("p", "w", "lam_g", "lam_x")]
+        obs = np.stack([pt.obs for pt in pts]) if r.field else None      # an "own" row calls with the handle's field
+        dp = np.stack([pt.dp for pt in pts])
+        dobs, rhs = stack([UR.row_dobs(r, k) for k in range(n)]), np.stack([UR.row_rhs(r, k) for k in range(n)])
+        calls = dict(sens=s.sens_batch(*a, dp=dp, gains="N", obstacles=obs),
+                     adjoint=s.sens_adjoint_batch(*a, np.stack([AR.row_cotangent(r, k) for k in range(n)]), obstacles=obs),
+                     update=s.sens_update_batch(*a, dp=dp, dobs=dobs, rhs=rhs, obstacles=obs),
+                     update_duals=s.sens_update_batch(*a, dp=dp, dobs=dobs, rhs=rhs, obstacles=obs, want_duals=True))
+        for call, res in calls.items():
+            for k, v in res.items():
+                if v is not None:
+                    out["sens_%s/%s/%s" % (SP.row_id(r), call, k)] = v.cpu().numpy()
+        print("%-52s info %s" % ("sens_" + SP.row_id(r), sorted({int(i) for c in calls for i in out["sens_%s/%s/info" % (SP.row_id(r), c)]})), flush=True)
+
+
+def run(path, groups=("solve", "lidar", "sens")):
+    out = {}
+    if "solve" in groups:
+        run_solve(out)
+    if "lidar" in groups:
+        run_lidar(out)
+    if "sens" in groups:
+        run_sens(out)
+    import nmpc_amd
+    np.savez_compressed(path, **out)
+    print("%d arrays of %s -> %s" % (len(out), nmpc_amd._lib.SO_PATH, path))
+
+
+def run_solve(out):
     import nmpc_amd
     from tests import helpers as Hh
     from tests import moving_obstacles_ref as MO
     from tests import test_gpu_phase_passes as PP
-    out = {}
     for name in PP.CASES:
         cfg, P, W0, F = PP.case_inputs(name)
         for duals in (False, True):
@@ -132,9 +173,6 @@ def run(path):
             s = nmpc_amd.NmpcSolver(Hh.to_product_cfg(cfg, max_iter=r.max_iter), max_batch=r.B, kernel=r.pin)
             assert int(s.kernel_for_batch(r.B)) == r.row[0], (r.row, s.kernel_for_batch(r.B))
             record(out, KV.row_id(r), s, P, W0)
-    run_lidar(out)
-    np.savez_compressed(path, **out)
-    print("%d arrays of %s -> %s" % (len(out), nmpc_amd._lib.SO_PATH, path))
 
 
 if __name__ == "__main__":
@@ -143,4 +181,4 @@ if __name__ == "__main__":
         bad = compare(a, b)
         print("%d arrays compared, %d differ%s" % (len(set(a) | set(b)), len(bad), (": " + ", ".join(bad)) if bad else ""))
         sys.exit(1 if bad else 0)
-    run(sys.argv[1])
+    run(sys.argv[1], *([tuple(sys.argv[2:])] if sys.argv[2:] else []))
