@@ -121,12 +121,16 @@ int32_t nmpc_create_opts(const nmpc_config_t *cfg, int32_t max_batch, const nmpc
  *   NMPC_QUERY_MAX_BATCH         the max_batch the handle was created for
  *   NMPC_QUERY_KERNEL_FOR_ORDERED_BATCH  arg = B: as NMPC_QUERY_KERNEL_FOR_BATCH for a call that carries a dispatch-order hint
  *                                (nmpc_solve_batch_ordered, nmpc_step_batch): the latency shape is kept for larger batches then
+ *   NMPC_QUERY_SENS_DIRS_PER_PASS  how many directions of nmpc_sens_update_batch_multi the handle's kernel carries through one pass of its stage
+ *                                recursion (64 - 5 m: the lanes of a wavefront the stage matrix leaves free); a call with more directions repeats
+ *                                only the affine part of the recursion for every further group of that size
  */
 #define NMPC_QUERY_KERNEL_FOR_BATCH 1
 #define NMPC_QUERY_WORKSPACE_BYTES 2
 #define NMPC_QUERY_LDS_BYTES 3
 #define NMPC_QUERY_MAX_BATCH 4
 #define NMPC_QUERY_KERNEL_FOR_ORDERED_BATCH 5
+#define NMPC_QUERY_SENS_DIRS_PER_PASS 6
 int64_t nmpc_query(const nmpc_handle_t *h, int32_t what, int64_t arg);
 
 /* bytes of device workspace held by the handle */
@@ -397,6 +401,37 @@ int32_t nmpc_sens_update_batch(nmpc_handle_t *h, int32_t B, const double *p, con
 int32_t nmpc_sens_update_batch_duals(nmpc_handle_t *h, int32_t B, const double *p, const double *obs, int32_t obs_stages, const double *w,
                                      const double *lam_g, const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw,
                                      double *alpha, double *dlam_g, double *dlam_x, double *alpha_dual, int32_t *info, void *stream);
+
+/*
+ * Forward plan update for D directions in one launch: nmpc_sens_update_batch applied to D directions (dp, dobs, rhs)_d at the same primal-dual
+ * point (p, obs, obs_stages, w, lam_g, lam_x) of every instance — the columns of the plan's Jacobian dw / dp or dw / dobs, the corrections of one
+ * prepared plan for D candidate measurements or obstacle fields, D right-hand sides against one linearisation.  The part of the stage recursion
+ * that depends on the point only is done once, not D times.
+ *   dp    [B][D][n_p]          = [dx0; dxs] of direction d
+ *   dobs  [B][D][S][K][3]      S = obs_stages of the call
+ *   rhs   [B][D][n_var]
+ * each may be NULL, which means zero for every direction.
+ *   dw    [B][D][n_var]        required
+ *   alpha [B][D]               may be NULL; dw keeps its bits without it
+ *   info  [B]                  one verdict per instance: it depends on the point, not on the direction
+ * Per direction d the contract is that of nmpc_sens_update_batch, word for word: dw[b][d] minimises 1/2 dw' W dw + c_d' dw subject to
+ * dX_0 = dx0_d and the linearised defects, with c_d = -2 Q dxs_d on X_k, k < N, + M_o dobs_d - rhs_d, the terms of c_d at one entry added in the
+ * fixed order goal, rhs, obstacles in index order; alpha[b][d] is the step limit of (dw[b][d], dobs_d) over the same items, with the same items
+ * left out, and exactly 1.0 when nothing limits the step; the verdicts are those of nmpc_sens_batch, 2 before 1, and with either all D
+ * directions of the instance get dw = 0 and alpha = 0.  The bits of a direction's dw and alpha do not depend on D, on the slot d the direction
+ * stands in, or on what the other directions hold; the same inputs give the same bits.  They agree with nmpc_sens_update_batch on the same
+ * direction to rounding, not bit for bit: the two kernels are compiled separately.
+ * 1 <= D <= NMPC_SENS_MAX_DIRS, else NMPC_E_ARG; dw == NULL is NMPC_E_ARG (dw is where the call keeps a direction's feed-forward terms between
+ * its two passes).  The other argument errors are those of nmpc_sens_update_batch: null p, w, lam_g, lam_x or info with B > 0, B beyond
+ * max_batch, the field errors of the *_obs calls, dobs without obs; NMPC_E_UNSUPPORTED on handles that run on kernel 1 or 2.  Every check is made
+ * on the host before anything is launched.  The inputs are read-only; the call is stream-ordered with the handle's other calls and uses the
+ * handle's workspace between its two passes exactly as nmpc_sens_batch does (nmpc_workspace_bytes does not change); no solve result depends on it.
+ * Multiplier updates for many directions are not provided: nmpc_sens_update_batch_duals remains the call for them.
+ */
+#define NMPC_SENS_MAX_DIRS 64
+int32_t nmpc_sens_update_batch_multi(nmpc_handle_t *h, int32_t B, int32_t D, const double *p, const double *obs, int32_t obs_stages, const double *w,
+                                     const double *lam_g, const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw,
+                                     double *alpha, int32_t *info, void *stream);
 
 /*
  * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and

@@ -22,11 +22,13 @@ LIDAR_EXPORTS = ["nmpc_lidar_n_var", "nmpc_lidar_n_g", "nmpc_lidar_n_p", "nmpc_l
                  "nmpc_lidar_eval_batch", "nmpc_lidar_shift_batch", "nmpc_lidar_scan_batch", "nmpc_lidar_plant_batch"]
 DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", "nmpc_debug_workspace", "nmpc_debug_variant", "nmpc_debug_variant_of_config", "nmpc_debug_lidar_variant"]      # include/nmpc_debug.h
 QUERY_KERNEL_FOR_BATCH, QUERY_WORKSPACE_BYTES, QUERY_LDS_BYTES, QUERY_MAX_BATCH, QUERY_KERNEL_FOR_ORDERED_BATCH = 1, 2, 3, 4, 5      # NMPC_QUERY_* of include/nmpc.h
+QUERY_SENS_DIRS_PER_PASS = 6
+SENS_MAX_DIRS = 64      # NMPC_SENS_MAX_DIRS
 EXPORTS = ["nmpc_n_var", "nmpc_n_g", "nmpc_n_p", "nmpc_config_default", "nmpc_create", "nmpc_create_opts", "nmpc_query", "nmpc_destroy",
            "nmpc_workspace_bytes", "nmpc_solve_batch", "nmpc_solve_batch_ordered", "nmpc_step_batch", "nmpc_eval_batch", "nmpc_shift_batch", "nmpc_odometry_batch", "nmpc_version",
            "nmpc_solve_batch_obs", "nmpc_step_batch_obs", "nmpc_eval_batch_obs", "nmpc_solve_batch_duals", "nmpc_step_batch_duals", "nmpc_kkt_batch",
            "nmpc_eval_batch_ref", "nmpc_kkt_batch_ref", "nmpc_sens_batch", "nmpc_sens_adjoint_batch", "nmpc_sens_update_batch",
-           "nmpc_sens_update_batch_duals"]
+           "nmpc_sens_update_batch_duals", "nmpc_sens_update_batch_multi"]
 
 
 class CConfig(C.Structure):
@@ -114,6 +116,7 @@ def load():
     L.nmpc_sens_adjoint_batch.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_adjoint_batch.restype = i32
     L.nmpc_sens_update_batch.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch.restype = i32
     L.nmpc_sens_update_batch_duals.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch_duals.restype = i32
+    L.nmpc_sens_update_batch_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch_multi.restype = i32
     L.nmpc_eval_batch_ref.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp]; L.nmpc_eval_batch_ref.restype = i32
     L.nmpc_kkt_batch_ref.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]; L.nmpc_kkt_batch_ref.restype = i32
     L.nmpc_shift_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]; L.nmpc_shift_batch.restype = i32

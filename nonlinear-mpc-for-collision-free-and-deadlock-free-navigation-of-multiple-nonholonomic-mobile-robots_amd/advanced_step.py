@@ -91,3 +91,41 @@ class AdvancedStepController:
             self._plan = dict(p=torch.where(ok[:, None], pl["p"] + step[:, None] * dp, pl["p"]), w=w, lam_g=res["lam_g"], lam_x=res["lam_x"],
                               obstacles=obs, status=pl["status"])
         return res
+
+    def correct_scenarios(self, x0_candidates, xs=None, obstacles=None):
+        """correct() for D scenarios of every instance in one sens_update_multi launch: x0_candidates [B, D, n_x], xs [B, D, n_x] or None
+        (unchanged), obstacles [B, D] + the field shape of the prepared obstacles, or None (unchanged).  Returns dict(w [B, D, n_var],
+        u0 [B, D, n_u], step [B, D], alpha [B, D], info [B], corrected [B]): scenario d by the rule of correct() — step is 1 where alpha == 1 and
+        tau * alpha elsewhere, w = w_pred + step * dw where the solve's status and the update's verdict are both 0, the prepared plan in every
+        scenario elsewhere.  .last['uncorrected'] counts the instances as correct() does.  Multipliers are not moved: update_duals and commit
+        belong to correct()."""
+        if self._plan is None:
+            raise RuntimeError("correct_scenarios() needs a prepared plan: call prepare() first")
+        s, pl = self.solver, self._plan
+        torch = s.torch
+        nx, nu, N = s.cfg.nx, s.cfg.nu, s.cfg.N
+        B = pl["p"].shape[0]
+        x0c = torch.as_tensor(x0_candidates, dtype=torch.float64, device=s.device)
+        if x0c.dim() != 3 or x0c.shape[0] != B or x0c.shape[2] != nx:
+            raise ValueError(f"x0_candidates must have shape ({B}, D, {nx}), got {tuple(x0c.shape)}")
+        D = x0c.shape[1]
+        dp = torch.zeros((B, D, 2 * nx), dtype=torch.float64, device=s.device)
+        dp[:, :, :nx] = x0c - pl["p"][:, None, :nx]
+        if xs is not None:
+            dp[:, :, nx:] = s._dev(xs, (B, D, nx)) - pl["p"][:, None, nx:]
+        dobs = None
+        if obstacles is not None:
+            if pl["obstacles"] is None:
+                raise ValueError("obstacles= needs a plan prepared with obstacles=: the config's own field is not a per-instance parameter")
+            fshape = tuple(pl["obstacles"].shape[1:])
+            dobs = torch.as_tensor(obstacles, dtype=torch.float64, device=s.device).reshape((B, D) + fshape) - pl["obstacles"][:, None]
+        out = s.sens_update_multi(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"])
+        alpha, info = out["alpha"], out["info"]
+        step = torch.where(alpha == 1.0, alpha, self.tau * alpha)
+        ok = (pl["status"] == 0) & (info == 0)
+        wp = pl["w"][:, None, :]
+        w = torch.where(ok[:, None, None], wp + step[:, :, None] * out["dw"], wp.expand(B, D, wp.shape[2]))
+        self.last["info"] = info
+        self.last["uncorrected"] = int((~ok).sum())
+        uo = (N + 1) * nx
+        return dict(w=w, u0=w[:, :, uo: uo + nu], step=step, alpha=alpha, info=info, corrected=ok)

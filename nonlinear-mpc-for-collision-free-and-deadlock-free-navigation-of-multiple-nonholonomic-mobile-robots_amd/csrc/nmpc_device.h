@@ -117,6 +117,12 @@ hipError_t launch_sens_fwd(const KParams &P, int m, int B, const double *w, cons
 hipError_t launch_sens_dual(const KParams &P, int m, int B, const double *w, const double *lam_g, const double *lam_x, const double *dp, const double *dobs,
                             const double *rhs, const double *dw, int obs_stages, const int32_t *info, double *dlam_g, double *dlam_x, double *alpha_dual,
                             hipStream_t st, bool ofield);
+// the forward plan update for D directions (include/nmpc.h, nmpc_sens_update_batch_multi; nmpc_sens_multi.hip): dw [B][D][nvar] (required) and alpha [B][D]
+// or nullptr for dp [B][D][2 nx], dobs [B][D][obs_stages][K][3] (only with ofield) and rhs [B][D][nvar], each nullptr for zero; 1 <= D <= NMPC_SENS_MAX_DIRS;
+// info [B] and ws as launch_sens.  plan_dirs_per_pass: the directions one pass of the recursion carries for team size m (NMPC_QUERY_SENS_DIRS_PER_PASS)
+hipError_t launch_plan_dirs(const KParams &P, int m, int B, int D, const double *w, const double *lam_g, const double *lam_x, const double *dp, const double *dobs,
+                            const double *rhs, double *dw, double *alpha, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
+int plan_dirs_per_pass(int m);
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);
 hipError_t launch_odometry(long n, const double *odom, const double *init, double *pose, int wrap, hipStream_t st);

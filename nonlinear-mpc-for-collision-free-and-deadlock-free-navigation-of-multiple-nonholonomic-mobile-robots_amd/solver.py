@@ -408,6 +408,81 @@ class NmpcSolver:
                                                        info.data_ptr(), self._stream()), "nmpc_sens_update_batch")
         return dict(dw=dw, alpha=alpha, info=info)
 
+    @property
+    def sens_dirs_per_pass(self) -> int:
+        """how many directions of sens_update_multi the handle's kernel carries through one pass of its stage recursion (nmpc_query)"""
+        return int(self.lib.nmpc_query(self._h, _lib.QUERY_SENS_DIRS_PER_PASS, 0))
+
+    def sens_update_multi(self, p, w, lam_g, lam_x, dp=None, dobs=None, rhs=None, obstacles=None, want_alpha: bool = True):
+        """sens_update_batch for D directions at the same point of every instance, one launch (nmpc_sens_update_batch_multi): dp [B, D, n_p],
+        dobs [B, D, *field shape] (the field shape of `obstacles`: K, 3 or N, K, 3) and rhs [B, D, n_var], each None for zero and at least one
+        given; D, at most 64, is taken from whichever is given.  Returns dict(dw [B, D, n_var], alpha [B, D] | None, info [B]): slot d is what
+        sens_update_batch returns for direction d, to rounding; its bits do not depend on D or on the slot.  info is one verdict per instance;
+        with info != 0 all D slots get dw = 0 and alpha = 0.  The part of the recursion that depends on the point only is done once.
+        Needs a handle that returns multipliers (duals_supported())."""
+        torch = self.torch
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        ob = self._obstacles(obstacles, B) if obstacles is not None else None
+        if dobs is not None and ob is None:
+            raise ValueError("dobs needs obstacles=: the config's own field is not a per-instance parameter")
+        given = [a for a in (dp, dobs, rhs) if a is not None]
+        if not given:
+            raise ValueError("at least one of dp, dobs, rhs must be given: the number of directions is taken from it")
+        shapes = [tuple(getattr(a, "shape", np.shape(a))) for a in given]
+        if any(len(s) < 3 or s[0] != B or s[1] != shapes[0][1] for s in shapes):
+            raise ValueError(f"dp, dobs and rhs must be [{B}, D, ...] with one D, got {shapes}")
+        D = int(shapes[0][1])
+        if not 1 <= D <= _lib.SENS_MAX_DIRS:
+            raise ValueError(f"D = {D} directions: 1 .. {_lib.SENS_MAX_DIRS} per call")
+        dp = self._dev(dp, (B, D, self.n_p)) if dp is not None else None
+        rhs = self._dev(rhs, (B, D, self.n_var)) if rhs is not None else None
+        if dobs is not None:
+            fshape = tuple(getattr(obstacles, "shape", np.shape(obstacles)))[1:]
+            if tuple(getattr(dobs, "shape", np.shape(dobs))) != (B, D) + fshape:
+                raise ValueError("dobs must have the shape [B, D] + the field shape of obstacles")
+            dobs = self._dev(dobs, (B, D) + tuple(ob[0].shape[1:]))
+        dw = torch.empty((B, D, self.n_var), dtype=torch.float64, device=self.device)
+        alpha = torch.empty((B, D), dtype=torch.float64, device=self.device) if want_alpha else None
+        info = torch.empty(B, dtype=torch.int32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nmpc_sens_update_batch_multi(self._h, B, D, p.data_ptr(), ptr(ob[0]) if ob is not None else None, ob[1] if ob is not None else 0,
+                                                             w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), ptr(dp), ptr(dobs), ptr(rhs), dw.data_ptr(),
+                                                             ptr(alpha), info.data_ptr(), self._stream()), "nmpc_sens_update_batch_multi")
+        return dict(dw=dw, alpha=alpha, info=info)
+
+    def plan_jacobian(self, p, w, lam_g, lam_x, obstacles=None, wrt: str = "p"):
+        """The Jacobian of the plan at (w, lam_g, lam_x) by the linearisation sens_batch uses, from unit directions through sens_update_multi.
+        wrt="p": J [B, n_var, n_p] = dw*/dp (x0 columns, then xs columns), one launch.  wrt="obstacles": J [B, n_var, S K 3] = dw*/dobstacles,
+        columns in the order of the flattened field of `obstacles` ([B, K, 3]: S = 1; [B, N, K, 3]: S = N, the columns of entry 0 are zero), in
+        as many launches of at most 64 directions as that takes.  Returns dict(J, info): info [B] as in sens_batch; J of an instance with
+        info != 0 is zeros."""
+        torch = self.torch
+        if wrt not in ("p", "obstacles"):
+            raise ValueError(f'wrt must be "p" or "obstacles", got {wrt!r}')
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        if wrt == "p":
+            eye = torch.eye(self.n_p, dtype=torch.float64, device=self.device).expand(B, self.n_p, self.n_p)
+            r = self.sens_update_multi(p, w, lam_g, lam_x, dp=eye, obstacles=obstacles, want_alpha=False)
+            return dict(J=r["dw"].transpose(1, 2).contiguous(), info=r["info"])
+        if obstacles is None:
+            raise ValueError('wrt="obstacles" needs obstacles=: the config\'s own field is not a per-instance parameter')
+        fshape = tuple(getattr(obstacles, "shape", np.shape(obstacles)))[1:]
+        n = int(np.prod(fshape))
+        J = torch.empty((B, self.n_var, n), dtype=torch.float64, device=self.device)
+        info = None
+        for lo in range(0, n, _lib.SENS_MAX_DIRS):
+            hi = min(n, lo + _lib.SENS_MAX_DIRS)
+            unit = torch.zeros((hi - lo, n), dtype=torch.float64, device=self.device)
+            unit[torch.arange(hi - lo, device=self.device), torch.arange(lo, hi, device=self.device)] = 1.0
+            r = self.sens_update_multi(p, w, lam_g, lam_x, dobs=unit.reshape((1, hi - lo) + fshape).expand((B, hi - lo) + fshape), obstacles=obstacles, want_alpha=False)
+            J[:, :, lo:hi] = r["dw"].transpose(1, 2)
+            info = r["info"]
+        return dict(J=J, info=info)
+
     def shift_batch(self, p, w, plant: bool = True):
         """device warm-start shift (C6:160-169,460-465) and, if plant, x0 + T f(x0,u0) (casadi_test.py:17-26)."""
         torch = self.torch
