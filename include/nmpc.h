@@ -391,8 +391,8 @@ int32_t nmpc_sens_update_batch(nmpc_handle_t *h, int32_t B, const double *p, con
  *   alpha_dual [B]         the largest a in (0, 1] that keeps every multiplier's sign: min(1, min_i z_i / (-dz_i)) over the items with z_i > 0 and
  *                          dz_i < 0 — the inequality rows of (c) with z = -lam_g, dz = -dlam_g, and the bounds of (d) with z = |lam_x|,
  *                          dz = sign(lam_x) dlam_x.  1.0 exactly when nothing limits it.
- * With verdict 1 or 2 the instance's dlam_g and dlam_x are zeros and alpha_dual = 0 (dw = 0 and alpha = 0 as above).  The multiplier of p is not
- * updated here.
+ * With verdict 1 or 2 the instance's dlam_g and dlam_x are zeros and alpha_dual = 0 (dw = 0 and alpha = 0 as above).  The change of the
+ * multiplier of p, dlam_p, is an output of nmpc_sens_update_batch_multi_duals (below; D = 1 for one direction).
  * dlam_g, dlam_x and alpha_dual may each be NULL; dw, alpha and info are bit for bit those of nmpc_sens_update_batch on the same inputs (with all
  * three NULL this is that call), and every output keeps its bits when any of the others is left out.  The argument errors and handle rules are
  * those of nmpc_sens_update_batch.  nmpc_workspace_bytes does not change: the multipliers need no workspace; only a call that asks for them with
@@ -426,12 +426,42 @@ int32_t nmpc_sens_update_batch_duals(nmpc_handle_t *h, int32_t B, const double *
  * max_batch, the field errors of the *_obs calls, dobs without obs; NMPC_E_UNSUPPORTED on handles that run on kernel 1 or 2.  Every check is made
  * on the host before anything is launched.  The inputs are read-only; the call is stream-ordered with the handle's other calls and uses the
  * handle's workspace between its two passes exactly as nmpc_sens_batch does (nmpc_workspace_bytes does not change); no solve result depends on it.
- * Multiplier updates for many directions are not provided: nmpc_sens_update_batch_duals remains the call for them.
+ * The multiplier updates of the D directions: nmpc_sens_update_batch_multi_duals, below.
  */
 #define NMPC_SENS_MAX_DIRS 64
 int32_t nmpc_sens_update_batch_multi(nmpc_handle_t *h, int32_t B, int32_t D, const double *p, const double *obs, int32_t obs_stages, const double *w,
                                      const double *lam_g, const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw,
                                      double *alpha, int32_t *info, void *stream);
+
+/*
+ * Forward plan update for D directions with their multiplier updates: nmpc_sens_update_batch_multi, followed on the same stream by one launch
+ * that gives every direction the dlam that go with its dw — each corrected scenario w + a dw[b][d] keeps multipliers lam + a dlam[b][d], so
+ * nmpc_kkt_batch can certify it, nmpc_sens_* can linearise again at it, and it can become the base of a chained correction; with unit
+ * directions the outputs are the columns of d lam* / d p and d lam* / d obs.  The walk that gives the multipliers eliminates nothing, and what
+ * it needs of the point at a stage is formed once for the D directions.
+ *   dlam_g     [B][D][n_g]
+ *   dlam_x     [B][D][n_var]
+ *   alpha_dual [B][D]
+ * Per direction d the contract is (a)-(e) of nmpc_sens_update_batch_duals, word for word, with (dp, dobs, rhs)_d and dw[b][d]: the exact zeros
+ * (the inequality rows of stage 0, the pad rows, rows with lam_g,i >= 0; X_0, an unbounded heading, lam_x,j == 0), the items of alpha_dual, and
+ * alpha_dual == 1.0 exactly when nothing limits it.
+ *   dlam_p     [B][D][n_p]     the change of lam_p as defined under nmpc_solve_batch_duals: the x0 part equals dlam_g[b][d][:n_x], bit for bit; the
+ *                              xs part is 2 Q (sum_{k<N} dX_k - N dxs_d) with dX_k of dw[b][d], the sum taken in the order k = N-1, N-2, .., 0.
+ * The call is nmpc_sens_update_batch_multi and then that launch: dw, alpha and info are bit for bit those of nmpc_sens_update_batch_multi on
+ * the same inputs; with dlam_g, dlam_x, dlam_p and alpha_dual all NULL this is that call.  Each of the four may be NULL, and every output keeps
+ * its bits when any of the others is left out.  With verdict 1 or 2 all D directions of the instance get zeros in dlam_g, dlam_x and dlam_p and
+ * alpha_dual = 0 (dw = 0 and alpha = 0 as there).  The bits of a direction's outputs do not depend on D, on the slot d the direction stands in,
+ * or on what the other directions hold; no atomics, the same inputs give the same bits.  They agree with nmpc_sens_update_batch_duals on the
+ * same direction to rounding, not bit for bit: the kernels are compiled separately.
+ * The argument errors and handle rules are those of nmpc_sens_update_batch_multi — D outside 1 .. NMPC_SENS_MAX_DIRS, dw == NULL, null p, w,
+ * lam_g, lam_x or info with B > 0, B beyond max_batch, the field errors of the *_obs calls, dobs without obs: NMPC_E_ARG; handles that run on
+ * kernel 1 or 2: NMPC_E_UNSUPPORTED — every one checked on the host before anything is launched, and nothing is written on an error.  B == 0
+ * returns NMPC_OK.  The multipliers need no workspace: nmpc_workspace_bytes does not change.
+ */
+int32_t nmpc_sens_update_batch_multi_duals(nmpc_handle_t *h, int32_t B, int32_t D, const double *p, const double *obs, int32_t obs_stages, const double *w,
+                                           const double *lam_g, const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw,
+                                           double *alpha, double *dlam_g, double *dlam_x, double *dlam_p, double *alpha_dual, int32_t *info,
+                                           void *stream);
 
 /*
  * Pose references per stage: the cost and the KKT certificate of a trajectory-tracking problem.  The two calls below are nmpc_eval_batch(_obs) and

@@ -28,7 +28,7 @@ EXPORTS = ["nmpc_n_var", "nmpc_n_g", "nmpc_n_p", "nmpc_config_default", "nmpc_cr
            "nmpc_workspace_bytes", "nmpc_solve_batch", "nmpc_solve_batch_ordered", "nmpc_step_batch", "nmpc_eval_batch", "nmpc_shift_batch", "nmpc_odometry_batch", "nmpc_version",
            "nmpc_solve_batch_obs", "nmpc_step_batch_obs", "nmpc_eval_batch_obs", "nmpc_solve_batch_duals", "nmpc_step_batch_duals", "nmpc_kkt_batch",
            "nmpc_eval_batch_ref", "nmpc_kkt_batch_ref", "nmpc_sens_batch", "nmpc_sens_adjoint_batch", "nmpc_sens_update_batch",
-           "nmpc_sens_update_batch_duals", "nmpc_sens_update_batch_multi"]
+           "nmpc_sens_update_batch_duals", "nmpc_sens_update_batch_multi", "nmpc_sens_update_batch_multi_duals"]
 
 
 class CConfig(C.Structure):
@@ -117,6 +117,7 @@ def load():
     L.nmpc_sens_update_batch.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch.restype = i32
     L.nmpc_sens_update_batch_duals.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch_duals.restype = i32
     L.nmpc_sens_update_batch_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch_multi.restype = i32
+    L.nmpc_sens_update_batch_multi_duals.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch_multi_duals.restype = i32
     L.nmpc_eval_batch_ref.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp]; L.nmpc_eval_batch_ref.restype = i32
     L.nmpc_kkt_batch_ref.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]; L.nmpc_kkt_batch_ref.restype = i32
     L.nmpc_shift_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]; L.nmpc_shift_batch.restype = i32

@@ -28,7 +28,9 @@ class AdvancedStepController:
     same step; the prepared ones where corrected is False) and alpha_dual.
     correct(..., commit=True) implies update_duals and makes the corrected point the controller's base on the corrected instances:
     (p + step dp, obstacles + step dobs, w, lam_g, lam_x) replace the prepared ones there, the next correct() linearises at them and takes its
-    dp and dobs relative to them; the other instances keep their base.  With both flags off nothing changes."""
+    dp and dobs relative to them; the other instances keep their base.  With both flags off nothing changes.
+    correct_scenarios(...) is correct() for D scenarios in one launch; with update_duals=True every scenario keeps multipliers, and
+    commit_scenario(d) makes one of them the base as correct(..., commit=True) would."""
 
     def __init__(self, solver: NmpcSolver, tau: float = 0.99):
         if not solver.duals_supported():
@@ -39,6 +41,7 @@ class AdvancedStepController:
         self.tau = float(tau)
         self.last = {}
         self._plan = None
+        self._scenarios = None      # what the last correct_scenarios(update_duals=True) left for commit_scenario
 
     def prepare(self, p_pred, w0, obstacles=None, **solve_kw):
         s = self.solver
@@ -92,13 +95,16 @@ class AdvancedStepController:
                               obstacles=obs, status=pl["status"])
         return res
 
-    def correct_scenarios(self, x0_candidates, xs=None, obstacles=None):
+    def correct_scenarios(self, x0_candidates, xs=None, obstacles=None, update_duals: bool = False):
         """correct() for D scenarios of every instance in one sens_update_multi launch: x0_candidates [B, D, n_x], xs [B, D, n_x] or None
         (unchanged), obstacles [B, D] + the field shape of the prepared obstacles, or None (unchanged).  Returns dict(w [B, D, n_var],
         u0 [B, D, n_u], step [B, D], alpha [B, D], info [B], corrected [B]): scenario d by the rule of correct() — step is 1 where alpha == 1 and
         tau * alpha elsewhere, w = w_pred + step * dw where the solve's status and the update's verdict are both 0, the prepared plan in every
-        scenario elsewhere.  .last['uncorrected'] counts the instances as correct() does.  Multipliers are not moved: update_duals and commit
-        belong to correct()."""
+        scenario elsewhere.  .last['uncorrected'] counts the instances as correct() does.
+        update_duals=True runs nmpc_sens_update_batch_multi_duals: every scenario's multipliers move with its plan by the rule of
+        correct(update_duals=True) — the step is the smaller of the primal one and 1 where alpha_dual == 1, tau * alpha_dual elsewhere — and the
+        dict gains lam_g [B, D, n_g], lam_x [B, D, n_var] (the prepared ones in every scenario where corrected is False) and alpha_dual [B, D].
+        commit_scenario(d) then makes one of the scenarios the controller's base."""
         if self._plan is None:
             raise RuntimeError("correct_scenarios() needs a prepared plan: call prepare() first")
         s, pl = self.solver, self._plan
@@ -119,13 +125,53 @@ class AdvancedStepController:
                 raise ValueError("obstacles= needs a plan prepared with obstacles=: the config's own field is not a per-instance parameter")
             fshape = tuple(pl["obstacles"].shape[1:])
             dobs = torch.as_tensor(obstacles, dtype=torch.float64, device=s.device).reshape((B, D) + fshape) - pl["obstacles"][:, None]
-        out = s.sens_update_multi(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"])
+        if update_duals:
+            out = s.sens_update_multi(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"], want_duals=True)
+        else:
+            out = s.sens_update_multi(pl["p"], pl["w"], pl["lam_g"], pl["lam_x"], dp=dp, dobs=dobs, obstacles=pl["obstacles"])
         alpha, info = out["alpha"], out["info"]
         step = torch.where(alpha == 1.0, alpha, self.tau * alpha)
+        if update_duals:
+            ad = out["alpha_dual"]
+            step = torch.minimum(step, torch.where(ad == 1.0, ad, self.tau * ad))
         ok = (pl["status"] == 0) & (info == 0)
-        wp = pl["w"][:, None, :]
-        w = torch.where(ok[:, None, None], wp + step[:, :, None] * out["dw"], wp.expand(B, D, wp.shape[2]))
+        moved = lambda base, d: torch.where(ok[:, None, None], base[:, None, :] + step[:, :, None] * d, base[:, None, :].expand(B, D, base.shape[1]))
+        w = moved(pl["w"], out["dw"])
         self.last["info"] = info
         self.last["uncorrected"] = int((~ok).sum())
         uo = (N + 1) * nx
-        return dict(w=w, u0=w[:, :, uo: uo + nu], step=step, alpha=alpha, info=info, corrected=ok)
+        res = dict(w=w, u0=w[:, :, uo: uo + nu], step=step, alpha=alpha, info=info, corrected=ok)
+        self._scenarios = None
+        if update_duals:
+            res["lam_g"] = moved(pl["lam_g"], out["dlam_g"])
+            res["lam_x"] = moved(pl["lam_x"], out["dlam_x"])
+            res["alpha_dual"] = out["alpha_dual"]
+            self._scenarios = dict(plan=pl, dp=dp, dobs=dobs, step=step, ok=ok, w=w, lam_g=res["lam_g"], lam_x=res["lam_x"])
+        return res
+
+    def commit_scenario(self, d):
+        """After correct_scenarios(update_duals=True): scenario d (an int, or [B] indices, one scenario per instance) becomes the controller's
+        base on the corrected instances — (p + step dp, obstacles + step dobs, w, lam_g, lam_x) of that scenario replace the prepared ones there,
+        exactly what correct(..., commit=True) on that scenario would have left; the other instances keep their base.  The scenarios were taken
+        relative to the old base, so one commit uses them up: a second one, or one without a dual-updating correct_scenarios on the current
+        base before it, raises RuntimeError."""
+        sc = self._scenarios
+        if sc is None or sc["plan"] is not self._plan:
+            raise RuntimeError("commit_scenario() needs a correct_scenarios(update_duals=True) on the current base before it")
+        s, pl = self.solver, sc["plan"]
+        torch = s.torch
+        B, D = sc["step"].shape
+        idx = torch.as_tensor(d, dtype=torch.int64, device=sc["step"].device).reshape(-1)
+        if idx.numel() == 1:
+            idx = idx.expand(B)
+        if idx.numel() != B or bool(((idx < 0) | (idx >= D)).any()):
+            raise ValueError(f"d must be one scenario index or {B} of them, each in 0 .. {D - 1}")
+        rows = torch.arange(B, device=idx.device)
+        ok, step = sc["ok"], sc["step"][rows, idx]
+        obs = pl["obstacles"]
+        if sc["dobs"] is not None:
+            okf = ok.reshape((B,) + (1,) * (obs.dim() - 1))
+            obs = torch.where(okf, obs + step.reshape(okf.shape) * sc["dobs"][rows, idx], obs)
+        self._plan = dict(p=torch.where(ok[:, None], pl["p"] + step[:, None] * sc["dp"][rows, idx], pl["p"]), w=sc["w"][rows, idx],
+                          lam_g=sc["lam_g"][rows, idx], lam_x=sc["lam_x"][rows, idx], obstacles=obs, status=pl["status"])
+        self._scenarios = None

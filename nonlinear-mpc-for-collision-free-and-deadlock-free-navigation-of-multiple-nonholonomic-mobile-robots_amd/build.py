@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.environ.get("NMPC_LIBDIR") or os.path.join(ROOT, "lib")      # short in-tree path (see _lib.SO_PATH); NMPC_LIBDIR: build somewhere else (the forced-build test: the shared in-tree artefact is not replaced under running processes)
 SO = os.path.join(LIBDIR, "libnmpc_hip.so")
 INFO = os.path.join(LIBDIR, "build_info.json")    # what the last build() call did: compiled or reused, and the source hash
-SOURCES = ["nmpc_kernels.hip", "nmpc_solve_lds.hip", "nmpc_solve_col.hip", "nmpc_lidar.hip", "nmpc_sens.hip", "nmpc_sens_dual.hip", "nmpc_sens_multi.hip", "nmpc_api.cpp"]
+SOURCES = ["nmpc_kernels.hip", "nmpc_solve_lds.hip", "nmpc_solve_col.hip", "nmpc_lidar.hip", "nmpc_sens.hip", "nmpc_sens_dual.hip", "nmpc_sens_multi.hip", "nmpc_sens_dual_multi.hip", "nmpc_api.cpp"]
 # per-source code generation switches.  nmpc_lidar.hip: machine-level loop-invariant code motion hoists the 64-bit literals of log() / sincos()
 # out of the stage loops into vector registers, the allocator then spills them and reloads each one from scratch, with a full vmcnt wait, at
 # every use (496 scratch loads in the kernel, 6 per log); without the pass they are re-materialised where used (114).  nmpc_solve_col.hip:

@@ -524,6 +524,28 @@ int32_t nmpc_sens_update_batch_multi(nmpc_handle_t *h, int32_t B, int32_t D, con
     return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 
+int32_t nmpc_sens_update_batch_multi_duals(nmpc_handle_t *h, int32_t B, int32_t D, const double *p, const double *obs, int32_t obs_stages, const double *w,
+                                           const double *lam_g, const double *lam_x, const double *dp, const double *dobs, const double *rhs, double *dw,
+                                           double *alpha, double *dlam_g, double *dlam_x, double *dlam_p, double *alpha_dual, int32_t *info, void *stream)
+{
+    const int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    if (rc != NMPC_OK) return rc;
+    if (D < 1 || D > NMPC_SENS_MAX_DIRS || !dw) return NMPC_E_ARG;
+    if (dobs && !obs) return NMPC_E_ARG;
+    if (B == 0) return NMPC_OK;
+    if (!p || !w || !lam_g || !lam_x || !info) return NMPC_E_ARG;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    nmpc::KParams P = h->P;
+    if (obs) set_field(&P, h->cfg, obs, obs_stages);
+    // the update kernel exactly as nmpc_sens_update_batch_multi launches it, then the multipliers from its dw and verdicts on the same stream
+    hipError_t e = nmpc::launch_plan_dirs(P, h->cfg.m, B, D, w, lam_g, lam_x, dp, dobs, rhs, dw, alpha, obs_stages, info, h->ws, (hipStream_t)stream, obs != nullptr);
+    if (e == hipSuccess && (dlam_g || dlam_x || dlam_p || alpha_dual))
+        e = nmpc::launch_dual_dirs(P, h->cfg.m, B, D, w, lam_g, lam_x, dp, dobs, rhs, dw, obs_stages, info, dlam_g, dlam_x, dlam_p, alpha_dual, (hipStream_t)stream,
+                                   obs != nullptr);
+    return e == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
 /* ---- the *_ref entry points: a pose reference per instance, one row or one per stage, in place of the xs half of p */
 int32_t nmpc_eval_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *ref, int32_t ref_stages, const double *obs,
                             int32_t obs_stages, double *f, double *g, void *stream)

@@ -123,6 +123,12 @@ hipError_t launch_sens_dual(const KParams &P, int m, int B, const double *w, con
 hipError_t launch_plan_dirs(const KParams &P, int m, int B, int D, const double *w, const double *lam_g, const double *lam_x, const double *dp, const double *dobs,
                             const double *rhs, double *dw, double *alpha, int obs_stages, int32_t *info, double *ws, hipStream_t st, bool ofield);
 int plan_dirs_per_pass(int m);
+// the multiplier updates of the D directions (include/nmpc.h, nmpc_sens_update_batch_multi_duals; nmpc_sens_dual_multi.hip), launched behind launch_plan_dirs on
+// its stream: from that call's inputs, its dw [B][D][nvar] and its verdicts info [B], dlam_g [B][D][ng], dlam_x [B][D][nvar], dlam_p [B][D][2 nx] and
+// alpha_dual [B][D], each nullptr or written; no workspace
+hipError_t launch_dual_dirs(const KParams &P, int m, int B, int D, const double *w, const double *lam_g, const double *lam_x, const double *dp, const double *dobs,
+                            const double *rhs, const double *dw, int obs_stages, const int32_t *info, double *dlam_g, double *dlam_x, double *dlam_p,
+                            double *alpha_dual, hipStream_t st, bool ofield);
 hipError_t launch_shift(const KParams &P, int m, int B, const double *p, const double *w_in, double *w_next, double *x0n, int x0_stride, const int32_t *keep_status, hipStream_t st);      // x0_stride: doubles between the x0_next rows (0 = n_x); keep_status: instances with status 2 / 3 there are left untouched (or nullptr)
 hipError_t launch_order_by_iters(int B, const int32_t *iters, int32_t *order, hipStream_t st);
 hipError_t launch_odometry(long n, const double *odom, const double *init, double *pose, int wrap, hipStream_t st);

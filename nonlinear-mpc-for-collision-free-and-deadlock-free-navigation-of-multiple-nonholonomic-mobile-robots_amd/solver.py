@@ -413,12 +413,16 @@ class NmpcSolver:
         """how many directions of sens_update_multi the handle's kernel carries through one pass of its stage recursion (nmpc_query)"""
         return int(self.lib.nmpc_query(self._h, _lib.QUERY_SENS_DIRS_PER_PASS, 0))
 
-    def sens_update_multi(self, p, w, lam_g, lam_x, dp=None, dobs=None, rhs=None, obstacles=None, want_alpha: bool = True):
+    def sens_update_multi(self, p, w, lam_g, lam_x, dp=None, dobs=None, rhs=None, obstacles=None, want_alpha: bool = True, want_duals: bool = False):
         """sens_update_batch for D directions at the same point of every instance, one launch (nmpc_sens_update_batch_multi): dp [B, D, n_p],
         dobs [B, D, *field shape] (the field shape of `obstacles`: K, 3 or N, K, 3) and rhs [B, D, n_var], each None for zero and at least one
         given; D, at most 64, is taken from whichever is given.  Returns dict(dw [B, D, n_var], alpha [B, D] | None, info [B]): slot d is what
         sens_update_batch returns for direction d, to rounding; its bits do not depend on D or on the slot.  info is one verdict per instance;
         with info != 0 all D slots get dw = 0 and alpha = 0.  The part of the recursion that depends on the point only is done once.
+        want_duals=True (nmpc_sens_update_batch_multi_duals: the same launch, then one more on its stream) adds the multiplier updates of every
+        direction, dlam_g [B, D, n_g], dlam_x [B, D, n_var], dlam_p [B, D, n_p] (the change of lam_p: x0 part = dlam_g[..., :n_x], xs part
+        2 Q (sum_k dX_k - N dxs)) and alpha_dual [B, D], slot d what sens_update_batch(want_duals=True) returns for direction d, to rounding; dw,
+        alpha and info keep their bits; zeros and alpha_dual = 0 where info != 0.
         Needs a handle that returns multipliers (duals_supported())."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
@@ -448,40 +452,65 @@ class NmpcSolver:
         alpha = torch.empty((B, D), dtype=torch.float64, device=self.device) if want_alpha else None
         info = torch.empty(B, dtype=torch.int32, device=self.device)
         ptr = lambda t: t.data_ptr() if t is not None else None
+        if want_duals:
+            dlam_g = torch.empty((B, D, self.n_g), dtype=torch.float64, device=self.device)
+            dlam_x = torch.empty((B, D, self.n_var), dtype=torch.float64, device=self.device)
+            dlam_p = torch.empty((B, D, self.n_p), dtype=torch.float64, device=self.device)
+            alpha_dual = torch.empty((B, D), dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.nmpc_sens_update_batch_multi_duals(self._h, B, D, p.data_ptr(), ptr(ob[0]) if ob is not None else None, ob[1] if ob is not None else 0,
+                                                                       w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), ptr(dp), ptr(dobs), ptr(rhs), dw.data_ptr(),
+                                                                       ptr(alpha), dlam_g.data_ptr(), dlam_x.data_ptr(), dlam_p.data_ptr(), alpha_dual.data_ptr(),
+                                                                       info.data_ptr(), self._stream()), "nmpc_sens_update_batch_multi_duals")
+            return dict(dw=dw, alpha=alpha, info=info, dlam_g=dlam_g, dlam_x=dlam_x, dlam_p=dlam_p, alpha_dual=alpha_dual)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.nmpc_sens_update_batch_multi(self._h, B, D, p.data_ptr(), ptr(ob[0]) if ob is not None else None, ob[1] if ob is not None else 0,
                                                              w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), ptr(dp), ptr(dobs), ptr(rhs), dw.data_ptr(),
                                                              ptr(alpha), info.data_ptr(), self._stream()), "nmpc_sens_update_batch_multi")
         return dict(dw=dw, alpha=alpha, info=info)
 
-    def plan_jacobian(self, p, w, lam_g, lam_x, obstacles=None, wrt: str = "p"):
+    def plan_jacobian(self, p, w, lam_g, lam_x, obstacles=None, wrt: str = "p", want_duals: bool = False):
         """The Jacobian of the plan at (w, lam_g, lam_x) by the linearisation sens_batch uses, from unit directions through sens_update_multi.
         wrt="p": J [B, n_var, n_p] = dw*/dp (x0 columns, then xs columns), one launch.  wrt="obstacles": J [B, n_var, S K 3] = dw*/dobstacles,
         columns in the order of the flattened field of `obstacles` ([B, K, 3]: S = 1; [B, N, K, 3]: S = N, the columns of entry 0 are zero), in
         as many launches of at most 64 directions as that takes.  Returns dict(J, info): info [B] as in sens_batch; J of an instance with
-        info != 0 is zeros."""
+        info != 0 is zeros.  want_duals=True adds the Jacobians of the multipliers from the same launches (sens_update_multi(want_duals=True)):
+        J_lam_g [B, n_g, cols], J_lam_x [B, n_var, cols] and, for wrt="p", J_lam_p [B, n_p, n_p]."""
         torch = self.torch
         if wrt not in ("p", "obstacles"):
             raise ValueError(f'wrt must be "p" or "obstacles", got {wrt!r}')
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        cols = lambda t: t.transpose(1, 2).contiguous()
         if wrt == "p":
             eye = torch.eye(self.n_p, dtype=torch.float64, device=self.device).expand(B, self.n_p, self.n_p)
-            r = self.sens_update_multi(p, w, lam_g, lam_x, dp=eye, obstacles=obstacles, want_alpha=False)
-            return dict(J=r["dw"].transpose(1, 2).contiguous(), info=r["info"])
+            r = self.sens_update_multi(p, w, lam_g, lam_x, dp=eye, obstacles=obstacles, want_alpha=False, want_duals=want_duals)
+            out = dict(J=cols(r["dw"]), info=r["info"])
+            if want_duals:
+                out.update(J_lam_g=cols(r["dlam_g"]), J_lam_x=cols(r["dlam_x"]), J_lam_p=cols(r["dlam_p"]))
+            return out
         if obstacles is None:
             raise ValueError('wrt="obstacles" needs obstacles=: the config\'s own field is not a per-instance parameter')
         fshape = tuple(getattr(obstacles, "shape", np.shape(obstacles)))[1:]
         n = int(np.prod(fshape))
         J = torch.empty((B, self.n_var, n), dtype=torch.float64, device=self.device)
+        Jg = torch.empty((B, self.n_g, n), dtype=torch.float64, device=self.device) if want_duals else None
+        Jx = torch.empty((B, self.n_var, n), dtype=torch.float64, device=self.device) if want_duals else None
         info = None
         for lo in range(0, n, _lib.SENS_MAX_DIRS):
             hi = min(n, lo + _lib.SENS_MAX_DIRS)
             unit = torch.zeros((hi - lo, n), dtype=torch.float64, device=self.device)
             unit[torch.arange(hi - lo, device=self.device), torch.arange(lo, hi, device=self.device)] = 1.0
-            r = self.sens_update_multi(p, w, lam_g, lam_x, dobs=unit.reshape((1, hi - lo) + fshape).expand((B, hi - lo) + fshape), obstacles=obstacles, want_alpha=False)
+            r = self.sens_update_multi(p, w, lam_g, lam_x, dobs=unit.reshape((1, hi - lo) + fshape).expand((B, hi - lo) + fshape), obstacles=obstacles, want_alpha=False,
+                                       want_duals=want_duals)
             J[:, :, lo:hi] = r["dw"].transpose(1, 2)
+            if want_duals:
+                Jg[:, :, lo:hi] = r["dlam_g"].transpose(1, 2)
+                Jx[:, :, lo:hi] = r["dlam_x"].transpose(1, 2)
             info = r["info"]
-        return dict(J=J, info=info)
+        out = dict(J=J, info=info)
+        if want_duals:
+            out.update(J_lam_g=Jg, J_lam_x=Jx)
+        return out
 
     def shift_batch(self, p, w, plant: bool = True):
         """device warm-start shift (C6:160-169,460-465) and, if plant, x0 + T f(x0,u0) (casadi_test.py:17-26)."""
