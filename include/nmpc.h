@@ -473,10 +473,33 @@ int32_t nmpc_sens_update_batch_multi_duals(nmpc_handle_t *h, int32_t B, int32_t 
  * (obs, obs_stages): obs == NULL and obs_stages == 0 is the handle's own obstacle field, otherwise the per-instance field by the rules of the
  * *_obs calls.  The row layout, n_g and the bounds are those of the plain calls; g does not depend on the reference, and given ref equal to the
  * xs half of p (either S) the outputs are those of the plain calls.  In nmpc_kkt_batch_ref, grad f of stage k is 2 Q (X_k - xs_k): a point whose
- * multipliers certify it here is a KKT point of the tracking problem, whoever computed it.  The solve calls take no per-stage reference yet.
+ * multipliers certify it here is a KKT point of the tracking problem, whoever computed it.
  * Returns NMPC_E_ARG when ref == NULL with B > 0, when ref_stages is neither 1 nor N, or for the argument errors of the *_obs calls.  Both
  * work on every handle, like nmpc_eval_batch.
+ *
+ * The tracking solve.  nmpc_solve_batch_ref / nmpc_step_batch_ref are nmpc_solve_batch_duals / nmpc_step_batch_duals with the cost of stage k
+ * measured against row k of ref (the same ref [B][S][n_x], S = ref_stages, 1 or N, and the same stage rule as above): the interior-point
+ * iteration, its rescue ladder, the status codes, the bounds and NMPC_STATUS_INFEASIBLE_X0 are those of the plain solve, and only the gradient
+ * 2 Q (X_k - xs_k) of the cost knows the stage.  The xs half of p is NOT read (it may hold anything, NaN included); the x0 half is read as always.
+ *   (obs, obs_stages): obs == NULL and obs_stages == 0 is the handle's own obstacle field, otherwise the per-instance field by the rules of the
+ *   *_obs calls.  order and duals may be NULL; duals follows the rules of the *_duals calls.
+ *   Multipliers: the conventions of nmpc_solve_batch_duals with xs_k in place of xs: the initial block of lam_g carries 2 Q (X_0 - xs_0), and
+ *   the xs part of lam_p is 2 Q sum_{k<N} (X_k - xs_k), summed in the same order: -lam_p[n_x:] is the sensitivity of the optimal cost to a
+ *   common translation of every reference row.  The x0 part is as before.
+ *   The step call shifts the plan and steps the plant exactly as nmpc_step_batch does; ref is not written: the caller supplies the next
+ *   period's window of its path.
+ * DEFINING PROPERTY: given ref rows all equal to the xs half of p, with S = 1 or S = N, w_out, obj, status, iters, kkt and the multipliers are
+ * bit-identical to nmpc_solve_batch_duals on the same inputs.
+ * The calls run the column-per-lane kernel's tracking instantiations (every shape, chosen by B and order as for a *_obs call): handles that run
+ * on kernel 1 or 2 (a pin, or a horizon beyond the column kernel's LDS) get NMPC_E_UNSUPPORTED.  NMPC_E_ARG as for the two calls above and for
+ * the *_duals calls.  The sensitivity calls (nmpc_sens_*) take no p-dependent cost term and run unchanged at a tracking solution.
  */
+int32_t nmpc_solve_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *ref, int32_t ref_stages, const double *obs, int32_t obs_stages,
+                             const double *w0, double *w_out, double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order,
+                             const nmpc_duals_t *duals, void *stream);
+int32_t nmpc_step_batch_ref(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *ref, int32_t ref_stages, const double *obs,
+                            int32_t obs_stages, double *obj, int32_t *status, int32_t *iters, double *kkt, int32_t *order, const nmpc_duals_t *duals,
+                            void *stream);
 int32_t nmpc_eval_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *w, const double *ref, int32_t ref_stages, const double *obs,
                             int32_t obs_stages, double *f, double *g, void *stream);
 int32_t nmpc_kkt_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *ref, int32_t ref_stages, const double *obs, int32_t obs_stages,

@@ -43,6 +43,12 @@ int32_t nmpc_debug_variant(const nmpc_handle_t *h, int32_t B, int32_t ordered, i
 int32_t nmpc_debug_variant_of_config(const nmpc_config_t *cfg, const nmpc_options_t *opts, int32_t compute_units, int32_t B, int32_t ordered,
                                      int32_t obs_field, nmpc_debug_variant_t *out, int32_t *kernel);
 
+/* the same for the tracking solve nmpc_solve_batch_ref (obs_field != 0: with obs): the row (3, m, thb, flags | 8, threads) of
+   track_col_kernelILi{m}ELi{thb}ELi{flags}ELi{threads}E — flags in the name without the 8, always with the 4: the tracking kernel is instantiated
+   with the per-instance field only — and its LDS bytes.  No launch is made; NMPC_E_UNSUPPORTED off the column kernel. */
+int32_t nmpc_debug_track_variant_of_config(const nmpc_config_t *cfg, const nmpc_options_t *opts, int32_t compute_units, int32_t B, int32_t ordered,
+                                           int32_t obs_field, nmpc_debug_variant_t *out, int32_t *kernel);
+
 /* the kernel instantiation of one LIDAR solve launch (include/nmpc_lidar.h), as in its mangled name: lidar_solve_kernelILi{rays}ELi{waves}E */
 typedef struct nmpc_debug_lidar_variant {
     int32_t rays;           /* template ray count: 10 (the scripts' count, loops unrolled for it) or -1 (any other count, predicated) */

@@ -20,7 +20,7 @@ ERRORS = {-1: "NMPC_E_ARG", -2: "NMPC_E_UNSUPPORTED", -3: "NMPC_E_HIP", -4: "NMP
 
 LIDAR_EXPORTS = ["nmpc_lidar_n_var", "nmpc_lidar_n_g", "nmpc_lidar_n_p", "nmpc_lidar_create", "nmpc_lidar_destroy", "nmpc_lidar_solve_batch",
                  "nmpc_lidar_eval_batch", "nmpc_lidar_shift_batch", "nmpc_lidar_scan_batch", "nmpc_lidar_plant_batch"]
-DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", "nmpc_debug_workspace", "nmpc_debug_variant", "nmpc_debug_variant_of_config", "nmpc_debug_lidar_variant"]      # include/nmpc_debug.h
+DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", "nmpc_debug_workspace", "nmpc_debug_variant", "nmpc_debug_variant_of_config", "nmpc_debug_track_variant_of_config", "nmpc_debug_lidar_variant"]      # include/nmpc_debug.h
 QUERY_KERNEL_FOR_BATCH, QUERY_WORKSPACE_BYTES, QUERY_LDS_BYTES, QUERY_MAX_BATCH, QUERY_KERNEL_FOR_ORDERED_BATCH = 1, 2, 3, 4, 5      # NMPC_QUERY_* of include/nmpc.h
 QUERY_SENS_DIRS_PER_PASS = 6
 SENS_MAX_DIRS = 64      # NMPC_SENS_MAX_DIRS
@@ -28,7 +28,8 @@ EXPORTS = ["nmpc_n_var", "nmpc_n_g", "nmpc_n_p", "nmpc_config_default", "nmpc_cr
            "nmpc_workspace_bytes", "nmpc_solve_batch", "nmpc_solve_batch_ordered", "nmpc_step_batch", "nmpc_eval_batch", "nmpc_shift_batch", "nmpc_odometry_batch", "nmpc_version",
            "nmpc_solve_batch_obs", "nmpc_step_batch_obs", "nmpc_eval_batch_obs", "nmpc_solve_batch_duals", "nmpc_step_batch_duals", "nmpc_kkt_batch",
            "nmpc_eval_batch_ref", "nmpc_kkt_batch_ref", "nmpc_sens_batch", "nmpc_sens_adjoint_batch", "nmpc_sens_update_batch",
-           "nmpc_sens_update_batch_duals", "nmpc_sens_update_batch_multi", "nmpc_sens_update_batch_multi_duals"]
+           "nmpc_sens_update_batch_duals", "nmpc_sens_update_batch_multi", "nmpc_sens_update_batch_multi_duals",
+           "nmpc_solve_batch_ref", "nmpc_step_batch_ref"]
 
 
 class CConfig(C.Structure):
@@ -99,6 +100,7 @@ def load():
     L.nmpc_debug_variant.argtypes = [vp, i32, i32, i32, C.POINTER(CDebugVariant)]; L.nmpc_debug_variant.restype = i32
     L.nmpc_debug_variant_of_config.argtypes = [cp, C.POINTER(COptions), i32, i32, i32, i32, C.POINTER(CDebugVariant), C.POINTER(i32)]
     L.nmpc_debug_variant_of_config.restype = i32
+    L.nmpc_debug_track_variant_of_config.argtypes = L.nmpc_debug_variant_of_config.argtypes; L.nmpc_debug_track_variant_of_config.restype = i32
     L.nmpc_destroy.argtypes = [vp]; L.nmpc_destroy.restype = i32
     L.nmpc_workspace_bytes.argtypes = [vp]; L.nmpc_workspace_bytes.restype = C.c_int64
     L.nmpc_solve_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_solve_batch.restype = i32
@@ -120,6 +122,8 @@ def load():
     L.nmpc_sens_update_batch_multi_duals.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_sens_update_batch_multi_duals.restype = i32
     L.nmpc_eval_batch_ref.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp]; L.nmpc_eval_batch_ref.restype = i32
     L.nmpc_kkt_batch_ref.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]; L.nmpc_kkt_batch_ref.restype = i32
+    L.nmpc_solve_batch_ref.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, dp, vp]; L.nmpc_solve_batch_ref.restype = i32
+    L.nmpc_step_batch_ref.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, dp, vp]; L.nmpc_step_batch_ref.restype = i32
     L.nmpc_shift_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]; L.nmpc_shift_batch.restype = i32
     L.nmpc_odometry_batch.argtypes = [C.c_int64, vp, vp, vp, i32, vp]; L.nmpc_odometry_batch.restype = i32
     L.nmpc_version.argtypes = []; L.nmpc_version.restype = C.c_char_p

@@ -18,10 +18,12 @@ SOURCES = ["nmpc_kernels.hip", "nmpc_solve_lds.hip", "nmpc_solve_col.hip", "nmpc
 # same pass, measured A/B in one session (round 3): two robots +2.3 %, six +3.7 % (B = 16384: +5.2 %), composite +2.3 %, ten +-0.
 FILE_FLAGS = {"nmpc_lidar.hip": os.environ.get("NMPC_LIDAR_FLAGS", "-mllvm -disable-machine-licm").split(),
               "nmpc_solve_col.hip": os.environ.get("NMPC_COL_FLAGS", "-mllvm -disable-machine-licm").split()}
-# compile units: (source, object name, extra flags).  The column-per-lane kernel is compiled in six units, COL_UNITS = (first team size, last,
-# per-instance obstacle field): ~120 s each instead of ~350 s per field flag in one unit (see launch_col_unit in the source, whose table
-# NMPC_COL_UNITS names the same units); the first carries the host entry points; with NMPC_COL_ONLY_M (development) the source is one unit.
-COL_UNITS = [(1, 5, 0), (6, 8, 0), (9, 10, 0), (1, 5, 1), (6, 8, 1), (9, 10, 1)]
+# compile units: (source, object name, extra flags).  The column-per-lane kernel is compiled in nine units, COL_UNITS = (first team size, last,
+# 0 plain / 1 per-instance obstacle field / 2 the tracking kernel, which exists with that field only): ~120 s each instead of ~350 s per such
+# flag in one unit (see launch_col_unit in the source, whose table NMPC_COL_UNITS names the same units); the first carries the host entry
+# points; with NMPC_COL_ONLY_M (development) the source is one unit.  The units are independent: on 16 cores the three tracking units run
+# next to the other six and the wall time of a build stays that of its longest unit.
+COL_UNITS = [(1, 5, 0), (6, 8, 0), (9, 10, 0), (1, 5, 1), (6, 8, 1), (9, 10, 1), (1, 5, 2), (6, 8, 2), (9, 10, 2)]
 UNITS = [(s, s.rsplit(".", 1)[0], []) for s in SOURCES if s != "nmpc_solve_col.hip"] \
     + [("nmpc_solve_col.hip", "nmpc_solve_col_p%d" % (k + 1), ["-DNMPC_COL_UNIT=%d,%d,%d" % u] + (["-DNMPC_COL_ENTRY"] if k == 0 else []))
        for k, u in enumerate(COL_UNITS)]

@@ -219,6 +219,94 @@ def simulate_closed_loop_fleets(cfg, x0, goals, max_steps: int, fleets: int = 4,
 
 
 @dataclass
+class TrackingResult:
+    steps: int                        # control periods executed (= max_steps)
+    rms_error: "np.ndarray"           # [B] position tracking error ||xy(t) - xy_ref(t)|| over robots and periods 0 .. steps: root mean square
+    max_error: "np.ndarray"           # [B] ... its maximum
+    final_error: "np.ndarray"         # [B] ... at the last period
+    min_pair_distance: "np.ndarray"   # [B] smallest centre distance seen (inf for one robot)
+    clearance: "np.ndarray"           # [B] smallest distance to an obstacle's surface minus rob_dim (inf without obstacles)
+    collision_free: "np.ndarray"      # [B] bool: pair distances >= dmin - coll_tol and clearances >= margin - coll_tol at every period
+    failed_solves: int                # solves that did not return status 0
+    total_solves: int
+    states: Optional["np.ndarray"] = None   # [steps+1, B, n_x] when keep_states
+
+
+def simulate_tracking(solver: NmpcSolver, x0, reference_paths, max_steps: int, obstacle_paths=None, keep_states: bool = False,
+                      coll_tol: float = 1e-6) -> TrackingResult:
+    """Run B closed-loop trajectory-tracking episodes (the loop of AllScripts/mpc_control_trajectory_tracking.py, P = [x0; x_ref,1 .. x_ref,N], for
+    B swarms at once).  x0: [B, n_x]; reference_paths: [B, L, n_x], L >= max_steps + N: the pose every robot should have at every control
+    period.  Period t makes one nmpc_step_batch_ref (solve, guess shift and plant step on the device) on rows t .. t+N-1 — stage k of the
+    plan is measured against row t + k — and the state of period t is compared with row t.  obstacle_paths: as in simulate_closed_loop.
+    The control of a non-converged solve is applied as returned and counted in failed_solves."""
+    torch = solver.torch
+    cfg = solver.cfg
+    nx, m, N = cfg.nx, cfg.m, cfg.N
+    dev = solver.device
+    x = solver._dev(x0, (-1, nx)).clone()
+    B = x.shape[0]
+    ref = torch.as_tensor(reference_paths, dtype=torch.float64, device=dev)
+    if ref.dim() != 3 or ref.shape[0] != B or ref.shape[1] < max_steps + N or ref.shape[2] != nx:
+        raise ValueError(f"reference_paths must be [B, L, n_x] with B={B}, L >= max_steps + N = {max_steps + N}, n_x={nx}; got {tuple(ref.shape)}")
+    K = len(cfg.obstacles)
+    obs = torch.tensor(cfg.obstacles, dtype=torch.float64, device=dev).reshape(-1, 3) if K else None
+    paths = field = None
+    if obstacle_paths is not None:
+        paths = torch.as_tensor(obstacle_paths, dtype=torch.float64, device=dev)
+        if K == 0 or paths.dim() != 4 or paths.shape[0] != B or paths.shape[1] < max_steps + N or paths.shape[2] != K or paths.shape[3] != 3:
+            raise ValueError(f"obstacle_paths must be [B, L, K, 3] with B={B}, L >= max_steps + N = {max_steps + N}, K = len(cfg.obstacles) = {K} > 0; "
+                             f"got {tuple(paths.shape)}")
+        field = torch.empty((B, N, K, 3), dtype=torch.float64, device=dev)
+    w = torch.cat([x.repeat(1, N + 1), torch.zeros((B, N * cfg.nu), dtype=torch.float64, device=dev)], dim=1).contiguous()      # cold start (C6:398-400)
+    pbuf = torch.full((B, 2 * nx), float("nan"), dtype=torch.float64, device=dev)      # the xs half is never read by the tracking solve
+    window = torch.empty((B, N, nx), dtype=torch.float64, device=dev)
+    mind = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+    clear = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+    iu = torch.triu_indices(m, m, 1, device=dev)
+    sq = torch.zeros(B, dtype=torch.float64, device=dev)
+    emax = torch.zeros(B, dtype=torch.float64, device=dev)
+    err = None
+    states = []
+    failed = total = 0
+
+    def track(xc, t):
+        nonlocal mind, clear, sq, emax, err
+        xy = xc.reshape(B, m, 3)[:, :, :2]
+        e = (xy - ref[:, t].reshape(B, m, 3)[:, :, :2]).norm(dim=2)      # [B, m]
+        sq = sq + (e * e).sum(dim=1)
+        err = e.amax(dim=1)
+        emax = torch.maximum(emax, err)
+        if m > 1:
+            mind = torch.minimum(mind, (xy[:, iu[0]] - xy[:, iu[1]]).norm(dim=2).min(dim=1).values)
+        ot = paths[:, t] if paths is not None else (obs[None].expand(B, -1, -1) if obs is not None else None)
+        if ot is not None:
+            clear = torch.minimum(clear, ((xy[:, :, None, :] - ot[:, None, :, :2]).norm(dim=3) - cfg.rob_dim - ot[:, None, :, 2]).amin(dim=(1, 2)))
+        if keep_states:
+            states.append(xc.clone())
+
+    track(x, 0)
+    for t in range(max_steps):
+        window.copy_(ref[:, t:t + N])
+        if field is not None:
+            field.copy_(paths[:, t:t + N])
+        pbuf[:, :nx] = x
+        r = solver.step_batch(pbuf, w, obstacles=field, reference=window)
+        x = pbuf[:, :nx].clone()
+        total += B
+        failed += int((r["status"] != 0).sum())
+        track(x, t + 1)
+    ok = torch.ones(B, dtype=torch.bool, device=dev)
+    if m > 1:
+        ok &= mind >= cfg.dmin - coll_tol
+    if obs is not None:
+        ok &= clear >= cfg.margin - coll_tol
+    return TrackingResult(steps=max_steps, rms_error=(sq / (m * (max_steps + 1))).sqrt().cpu().numpy(), max_error=emax.cpu().numpy(),
+                          final_error=err.cpu().numpy(), min_pair_distance=mind.cpu().numpy(), clearance=clear.cpu().numpy(),
+                          collision_free=ok.cpu().numpy(), failed_solves=failed, total_solves=total,
+                          states=torch.stack(states).cpu().numpy() if keep_states else None)
+
+
+@dataclass
 class LidarEpisodeResult:
     steps: int                      # control periods executed
     arrived: "np.ndarray"           # [B] bool: the last goal was reached (V4:284-291: goal_idx > ng)

@@ -38,6 +38,7 @@ struct nmpc_handle {
     int32_t *ord_chk;    // [max_batch + 1] permutation check of a dispatch-order hint: counts, then the "bad" flag
     int32_t *it_buf;     // [max_batch] iteration counts of nmpc_step_batch when the caller passes iters == NULL
     int32_t *st_buf;     // [max_batch] statuses of nmpc_step_batch when the caller passes status == NULL (the in-place update skips failed instances)
+    double *cfg_field;   // [n_obs][3] device copy of the config's obstacle field: what a tracking solve without obs reads as its per-instance field (stride 0); nullptr without obstacles
     double *dw_buf;      // [max_batch][n_var] the dw that nmpc_sens_update_batch_duals computes its multipliers from when the caller passes dw == NULL; allocated by the first such call
 };
 
@@ -152,9 +153,12 @@ static Selector selector_fill(const nmpc::KParams &P, int pin, int cus)
 // The launch a solve of B instances makes: which kernel, in which shape, and the instantiation (the select_* function of that kernel).
 // solve_impl() launches by it; nmpc_query() and the nmpc_debug_variant* descriptors report it.  ordered: the call carries a dispatch-order
 // hint; needs_column: it passes an obstacle field or asks for the multipliers, which only the column kernel serves; field: the instantiation
-// reads the per-instance obstacle field.  false: the call is unsupported on this configuration (needs_column off the column kernel).
-static bool solve_plan(const nmpc::KParams &P, const Selector &s, int32_t B, bool ordered, bool needs_column, bool field, SolvePlan *pl)
+// reads the per-instance obstacle field; track: a tracking solve (the *_ref solve calls), which needs the column kernel and runs its tracking
+// instantiation in the shape the same call without a reference would get.  false: the call is unsupported on this configuration (needs_column
+// off the column kernel).
+static bool solve_plan(const nmpc::KParams &P, const Selector &s, int32_t B, bool ordered, bool needs_column, bool field, SolvePlan *pl, bool track = false)
 {
+    needs_column = needs_column || track;
     if (needs_column && s.base != KERN_COL) return false;      // horizon beyond the column kernel's LDS, or a pin to kernel 1 / 2
     // Kernel.  The column-per-lane kernel (one wave per instance, two instances per SIMD up to six robots) is the
     // throughput path.  A batch that cannot fill those slots is a latency problem instead (the launch lasts as long as its longest
@@ -190,6 +194,7 @@ static bool solve_plan(const nmpc::KParams &P, const Selector &s, int32_t B, boo
                 : (s.pin == 5 || (m >= 5 && m <= 6 && items > 1000 && B <= 2 * s.lat_slots4)) ? SHAPE_LAT4 : SHAPE_LAT2;
     return kern == KERN_HBM   ? nmpc::select_solve(P, m, B, &pl->v)
            : kern == KERN_LDS ? nmpc::select_solve_lds(P, m, B, &pl->v)
+           : track            ? nmpc::select_track_col(P, m, pl->shape, &pl->v)
                               : nmpc::select_solve_col(P, m, pl->shape, field, &pl->v);
 }
 
@@ -216,6 +221,11 @@ static int32_t handle_init(nmpc_handle *h, const nmpc_config_t *cfg, int32_t max
     if (hipMalloc((void **)&h->it_buf, sizeof(int32_t) * (size_t)max_batch) != hipSuccess) return NMPC_E_NOMEM;
     if (hipMalloc((void **)&h->st_buf, sizeof(int32_t) * (size_t)max_batch) != hipSuccess) return NMPC_E_NOMEM;
     h->P.trace_inst = opts ? opts->trace_instance : -1;
+    if (cfg->n_obs > 0) {
+        const size_t nb = sizeof(double) * 3 * (size_t)cfg->n_obs;
+        if (hipMalloc((void **)&h->cfg_field, nb) != hipSuccess) return NMPC_E_NOMEM;
+        if (hipMemcpy(h->cfg_field, cfg->obs, nb, hipMemcpyHostToDevice) != hipSuccess) return NMPC_E_HIP;
+    }
     return NMPC_OK;
 }
 
@@ -243,6 +253,7 @@ int32_t nmpc_destroy(nmpc_handle_t *h)
     if (h->it_buf) (void)hipFree(h->it_buf);
     if (h->st_buf) (void)hipFree(h->st_buf);
     if (h->dw_buf) (void)hipFree(h->dw_buf);
+    if (h->cfg_field) (void)hipFree(h->cfg_field);
     free(h);
     return NMPC_OK;
 }
@@ -288,15 +299,17 @@ static bool wants_duals(const nmpc_duals_t *d) { return d && (d->lam_g || d->lam
 
 // obs != NULL: the obstacle field of the instances, [B][obs_stages][n_obs][3] (checked by call_check), read by the column kernel's
 // per-instance field instantiations; handles that run on kernel 1 or 2 have none.  duals: the multiplier outputs of the *_duals entry points,
-// written by the column kernel's epilogue (nullptr, or all members nullptr: the plain call)
+// written by the column kernel's epilogue (nullptr, or all members nullptr: the plain call).  ref != NULL: the tracking solve, ref
+// [B][ref_stages][n_x] (checked by ref_check) read by the column kernel's tracking instantiations, which exist with the per-instance field only:
+// without obs every instance reads the handle's device copy of the config's field
 static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
                           int32_t *iters, double *kkt, const int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0,
-                          const nmpc_duals_t *duals = nullptr)
+                          const nmpc_duals_t *duals = nullptr, const double *ref = nullptr, int32_t ref_stages = 0)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
     const bool du = wants_duals(duals);
     SolvePlan pl;
-    if (!solve_plan(h->P, h->sel, B, order != nullptr, obs || du, obs != nullptr, &pl)) return NMPC_E_UNSUPPORTED;
+    if (!solve_plan(h->P, h->sel, B, order != nullptr, obs || du, obs != nullptr, &pl, ref != nullptr)) return NMPC_E_UNSUPPORTED;
     if (B == 0) return NMPC_OK;      /* empty batch: nothing to read or write, pointers may be null */
     if (!p || !w0 || !w_out) return NMPC_E_ARG;
     DeviceScope dev(h->device);
@@ -305,9 +318,10 @@ static int32_t solve_impl(nmpc_handle_t *h, int32_t B, const double *p, const do
     P.order = order;
     P.order_bad = h->ord_chk + B;
     if (obs) set_field(&P, h->cfg, obs, obs_stages);
+    else if (ref) { P.ofield.ptr = h->cfg_field; P.ofield.istride = 0; P.ofield.sstride = 0; }
     if (du) { P.lam_g = duals->lam_g; P.lam_x = duals->lam_x; P.lam_p = duals->lam_p; }
     if (order && nmpc::launch_order_check(B, order, h->ord_chk, h->ord_chk + B, (hipStream_t)stream) != hipSuccess) return NMPC_E_HIP;
-    const nmpc::SolveArgs a{p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof};
+    const nmpc::SolveArgs a{p, w0, w_out, obj, status, iters, kkt, h->ws, h->prof, ref ? pose_ref(h->cfg, p, ref, ref_stages) : nmpc::PoseRef{nullptr, 0, 0}};
     hipError_t e = pl.v.kernel == KERN_HBM   ? nmpc::launch_solve(P, pl.v, B, a, (hipStream_t)stream)
                    : pl.v.kernel == KERN_LDS ? nmpc::launch_solve_lds(P, pl.v, B, a, (hipStream_t)stream)
                                              : nmpc::launch_solve_col(P, pl.v, B, a, (hipStream_t)stream);
@@ -327,16 +341,17 @@ int32_t nmpc_solve_batch_ordered(nmpc_handle_t *h, int32_t B, const double *p, c
 }
 
 static int32_t step_impl(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, double *obj, int32_t *status, int32_t *iters, double *kkt,
-                         int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0, const nmpc_duals_t *duals = nullptr)
+                         int32_t *order, void *stream, const double *obs = nullptr, int32_t obs_stages = 0, const nmpc_duals_t *duals = nullptr,
+                         const double *ref = nullptr, int32_t ref_stages = 0)
 {
     if (!h || B < 0 || B > h->max_batch) return NMPC_E_ARG;
-    if ((obs || wants_duals(duals)) && h->sel.base != KERN_COL) return NMPC_E_UNSUPPORTED;
+    if ((obs || ref || wants_duals(duals)) && h->sel.base != KERN_COL) return NMPC_E_UNSUPPORTED;
     if (B == 0) return NMPC_OK;
     if (!p || !w || !w_sol || w == w_sol) return NMPC_E_ARG;
     int32_t *it = iters ? iters : h->it_buf;
     int32_t *stt = status ? status : h->st_buf;
     // 1. the solve, dispatched in the caller's order (checked to be a permutation; ignored otherwise)
-    int32_t rc = solve_impl(h, B, p, w, w_sol, obj, stt, it, kkt, order, stream, obs, obs_stages, duals);      // the multipliers of this period's w_sol
+    int32_t rc = solve_impl(h, B, p, w, w_sol, obj, stt, it, kkt, order, stream, obs, obs_stages, duals, ref, ref_stages);      // the multipliers of this period's w_sol
     if (rc != NMPC_OK) return rc;
     DeviceScope dev(h->device);
     if (!dev.ok) return NMPC_E_HIP;
@@ -563,6 +578,26 @@ int32_t nmpc_kkt_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const d
     return rc != NMPC_OK ? rc : kkt_impl(h, B, p, ref, ref_stages, obs, obs_stages, w, lam_g, lam_x, res, grad_lag, stream);
 }
 
+int32_t nmpc_solve_batch_ref(nmpc_handle_t *h, int32_t B, const double *p, const double *ref, int32_t ref_stages, const double *obs, int32_t obs_stages,
+                             const double *w0, double *w_out, double *obj, int32_t *status, int32_t *iters, double *kkt, const int32_t *order,
+                             const nmpc_duals_t *duals, void *stream)
+{
+    int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    if (rc == NMPC_OK) rc = ref_check(h, B, ref, ref_stages);
+    if (rc != NMPC_OK || B == 0) return rc;
+    return solve_impl(h, B, p, w0, w_out, obj, status, iters, kkt, order, stream, obs, obs_stages, duals, ref, ref_stages);
+}
+
+int32_t nmpc_step_batch_ref(nmpc_handle_t *h, int32_t B, double *p, double *w, double *w_sol, const double *ref, int32_t ref_stages, const double *obs,
+                            int32_t obs_stages, double *obj, int32_t *status, int32_t *iters, double *kkt, int32_t *order, const nmpc_duals_t *duals,
+                            void *stream)
+{
+    int32_t rc = call_check(h, B, obs, obs_stages, CK_BOUNDED | CK_OPT_FIELD | CK_COLUMN);
+    if (rc == NMPC_OK) rc = ref_check(h, B, ref, ref_stages);
+    if (rc != NMPC_OK || B == 0) return rc;
+    return step_impl(h, B, p, w, w_sol, obj, status, iters, kkt, order, stream, obs, obs_stages, duals, ref, ref_stages);
+}
+
 int32_t nmpc_shift_batch(nmpc_handle_t *h, int32_t B, const double *p_in, const double *w_in, double *w_next, double *x0_next, void *stream)
 {
     if (!h || B < 0) return NMPC_E_ARG;
@@ -644,11 +679,11 @@ int64_t nmpc_debug_workspace(nmpc_handle_t *h, int32_t inst, double *out, int64_
 
 /* the descriptor of a plan, with the codes of the call it describes */
 static int32_t describe(const nmpc_config_t &cfg, const nmpc::KParams &P, const Selector &sel, int32_t B, int32_t ordered, int32_t obs_field,
-                        nmpc_debug_variant_t *out, int32_t *kernel)
+                        nmpc_debug_variant_t *out, int32_t *kernel, bool track = false)
 {
     if (obs_field && cfg.n_obs == 0) return NMPC_E_ARG;      // as call_check()
     SolvePlan pl;
-    if (!solve_plan(P, sel, B, ordered != 0, obs_field != 0, obs_field != 0, &pl)) return NMPC_E_UNSUPPORTED;
+    if (!solve_plan(P, sel, B, ordered != 0, obs_field != 0, obs_field != 0, &pl, track)) return NMPC_E_UNSUPPORTED;
     const nmpc::SolveVariant &v = pl.v;
     out->kernel = v.kernel; out->m = v.m; out->thb = v.thb; out->flags = v.flags; out->threads = v.threads; out->lds_bytes = (int64_t)v.lds;
     if (kernel) *kernel = pl.kernel;
@@ -672,6 +707,18 @@ int32_t nmpc_debug_variant_of_config(const nmpc_config_t *cfg, const nmpc_option
     nmpc::KParams P;
     fill_params(cfg, &P);
     return describe(*cfg, P, selector_fill(P, opts ? opts->kernel : 0, compute_units), B, ordered, obs_field, out, kernel);
+}
+
+/* the same for a tracking solve (nmpc_solve_batch_ref) of B instances: the tracking row (3, m, thb, flags | 8, threads) and its LDS bytes */
+int32_t nmpc_debug_track_variant_of_config(const nmpc_config_t *cfg, const nmpc_options_t *opts, int32_t compute_units, int32_t B, int32_t ordered,
+                                           int32_t obs_field, nmpc_debug_variant_t *out, int32_t *kernel)
+{
+    if (!cfg || !out || compute_units < 1 || B < 0) return NMPC_E_ARG;
+    const int32_t rc = config_check(cfg, opts);
+    if (rc != NMPC_OK) return rc;
+    nmpc::KParams P;
+    fill_params(cfg, &P);
+    return describe(*cfg, P, selector_fill(P, opts ? opts->kernel : 0, compute_units), B, ordered, obs_field, out, kernel, true);
 }
 
 #ifndef NMPC_SRC_HASH

@@ -58,7 +58,8 @@ struct HbmWs {
 // The pose reference of the cost as eval_kernel and kkt_residual_kernel read it, sum_k (X_k - xs_k)' Q (X_k - xs_k): instance b's rows start at
 // ptr + b * istride and stage k reads row k * sstride.  The plain calls point it at the xs half of p (ptr = p + n_x, istride = 2 n_x, sstride = 0),
 // the *_ref calls at ref [B][S][n_x] (istride = S n_x; sstride = n_x when S = N, else 0).  A kernel argument of its own: KParams, which the solve
-// kernels share, keeps its layout.
+// kernels share, keeps its layout.  The column kernel's tracking instantiations (track_col_kernel, nmpc_solve_batch_ref) read the same struct
+// through PoseRows (nmpc_solve_common.h).
 struct PoseRef {
     const double *ptr;
     int32_t istride, sstride;
@@ -73,13 +74,14 @@ enum { SHAPE_TP = 0, SHAPE_LAT2 = 1, SHAPE_LAT4 = 2 };
 // solve_col_kernel<M, THB, DL, TPB> (3), and its dynamic LDS.  Filled by the select_* function of each kernel; its launcher launches exactly
 // this instantiation (hipErrorInvalidValue where it does not exist) and selects nothing itself.
 struct SolveVariant {
-    int kernel, m, thb, flags, threads;      // kernel: KERN_HBM / KERN_LDS / KERN_COL; thb: 0 for kernel 1 (no such template argument); flags: DL of the column kernel, else 0
+    int kernel, m, thb, flags, threads;      // kernel: KERN_HBM / KERN_LDS / KERN_COL; thb: 0 for kernel 1 (no such template argument); flags: DL of the column kernel (bit 2: per-instance obstacle field), bit 3 (8): track_col_kernel<M, THB, DL, TPB> with DL = flags - 8; else 0
     size_t lds;
 };
 // false: team size not instantiated
 bool select_solve(const KParams &P, int m, int B, SolveVariant *v);
 bool select_solve_lds(const KParams &P, int m, int B, SolveVariant *v);
 bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVariant *v);      // shape: SHAPE_*; ofield: the per-instance obstacle field P.ofield
+bool select_track_col(const KParams &P, int m, int shape, SolveVariant *v);      // the tracking kernel (always with P.ofield): flags carry bit 3
 
 // device pointers of one solve call: inputs, outputs (each of obj .. kkt may be nullptr), the handle's workspace and profile counters
 struct SolveArgs {
@@ -88,6 +90,7 @@ struct SolveArgs {
     int32_t *status, *iters;
     double *kkt, *ws;
     long long *prof;
+    PoseRef ref;      // the tracking kernel's launches only: the per-stage pose reference of the call
 };
 hipError_t launch_solve(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st);
 hipError_t launch_solve_lds(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st);

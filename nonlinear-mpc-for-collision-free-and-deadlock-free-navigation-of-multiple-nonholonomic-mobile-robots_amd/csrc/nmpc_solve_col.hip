@@ -166,11 +166,13 @@ template <int M_, int THB> struct ColLayout {
 // DL: where the instance keeps its data, bits 0-1 (0 .. 3, see the slack / dual arrays below); bit 2 (NMPC_DL_OBS): the obstacle field is the
 // per-instance array of the *_obs entry points instead of the kernel argument (ObsField, nmpc_solve_common.h) — a separate instantiation, so
 // the plain ones carry no trace of it.
-template <int M_, int THB, int DL, int TPBK = 64>
-__global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_col_kernel(const KParams P, const double *__restrict__ p_in, const double *__restrict__ w0,
-                                                        double *__restrict__ w_out, double *__restrict__ obj_out,
-                                                        int32_t *__restrict__ status_out, int32_t *__restrict__ iters_out,
-                                                        double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
+// TR: the pose reference of the cost is the goal of p (0: solve_col_kernel) or the per-stage rows of R (1: track_col_kernel), see PoseRows
+// (nmpc_solve_common.h).  The body is this one function; the two kernels below are its only callers.
+template <int M_, int THB, int DL, int TPBK, int TR>
+__device__ __forceinline__ void solve_col_body(const KParams &P, const PoseRef &R, const double *__restrict__ p_in, const double *__restrict__ w0,
+                                               double *__restrict__ w_out, double *__restrict__ obj_out,
+                                               int32_t *__restrict__ status_out, int32_t *__restrict__ iters_out,
+                                               double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
 {
     using G = GC<M_, THB>;
     using W = WsLayout<M_, THB>;
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     double *FS = RV, *PK = RV;            // QP multipliers of the adjoint recursion (FS [KTS]: staged stage factor, only the > 32-control forward path)
     constexpr int RG0 = G::KTS > G::PACK ? G::KTS : G::PACK;
     static_assert(RG0 <= ColLayout<M_, THB>::RG, "the scratch region holds this kernel's staged pack");
-    double *XS = sm + L.XS;               // [NX]
+    const PoseRows<TR> XR(sm + L.XS, R, inst);      // XR(k, c): the pose stage k's cost measures X_k against (the goal [NX] in LDS, or the reference's row k)
     double *RED = sm + L.RED;             // [8]
     // slacks and duals of the inequality rows: in the instance's workspace (HBM/L2) for the larger teams, whose LDS budget of
     // 20 KB (eight instances per CU) they would break; in LDS (DL = 1) for up to four robots when they fit that budget — there the
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     // ---- load start, pin X_0, push into the interior of the simple bounds (IPOPT bound_push)
     const Bounds bnd{P, THB};      // the simple bounds (nmpc_solve_common.h)
     constexpr double bp = NMPC_BOUND_PUSH;
-    for (int c = tid; c < NX; c += TPB) XS[c] = pp[NX + c];
+    if constexpr (!TR) for (int c = tid; c < NX; c += TPB) sm[L.XS + c] = pp[NX + c];      // the goal; a tracking call never reads the xs half of p
     for (int e = tid; e < N1 * NX; e += TPB) {
         int k = e / NX, c = e - k * NX;
         double v = (k == 0) ? pp[c] : wi[e];
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             if (a == 0.0) { s = SN[it]; c = CS[it]; } else sincos(x2, &s, &c);
             double c0 = fabs(defect_xy(n0, x0, T * u0, c)), c1 = fabs(defect_xy(n1, x1, T * u0, s)), c2 = fabs(defect_th(n2, x2, T, u1));
             t += c0 + c1 + c2; mc = fmax(mc, fmax(c0, fmax(c1, c2)));
-            double e0 = x0 - XS[3 * i], e1 = x1 - XS[3 * i + 1], e2 = x2 - XS[3 * i + 2];
+            double e0 = x0 - XR(k, 3 * i), e1 = x1 - XR(k, 3 * i + 1), e2 = x2 - XR(k, 3 * i + 2);
             fs += P.q[0] * e0 * e0 + P.q[1] * e1 * e1 + P.q[2] * e2 * e2 + P.r[0] * u0 * u0 + P.r[1] * u1 * u1;
             // control bounds of stage k
             brow(SUL[ou], U[ou] + P.vmax, DU[ou], u0 + P.vmax); brow(SUU[ou], P.vmax - U[ou], -DU[ou], P.vmax - u0);
@@ -492,8 +494,8 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     // ---- terms of the stage packs (B0), each written ONCE.  The fused pass of phase A and stage_packs_a / _b call them with the values they
     //      have loaded, so both paths form every pack entry by the same expression, operand for operand (their results are bit-identical).
     struct XTerms { double g0 = 0.0, g1 = 0.0, g2 = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, hxy = 0.0; };      // state entries of one (stage, robot): x-gradient, diagonal additions, xy cross term
-    auto pk_cost = [&](XTerms &t, const double *x, int i) __attribute__((always_inline)) {      // tracking cost (stages 1 .. N-1)
-        t.g0 = 2 * P.q[0] * (x[3 * i] - XS[3 * i]); t.g1 = 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]); t.g2 = 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]);
+    auto pk_cost = [&](XTerms &t, const double *x, int k, int i) __attribute__((always_inline)) {      // tracking cost of the stage-k state x (stages 1 .. N-1)
+        t.g0 = 2 * P.q[0] * (x[3 * i] - XR(k, 3 * i)); t.g1 = 2 * P.q[1] * (x[3 * i + 1] - XR(k, 3 * i + 1)); t.g2 = 2 * P.q[2] * (x[3 * i + 2] - XR(k, 3 * i + 2));
         t.h0 = 2 * P.q[0]; t.h1 = 2 * P.q[1]; t.h2 = 2 * P.q[2];
     };
     // a bound row: v = mu/s - sigma (h - s), sigma = z/s, lower row gradient +1, upper row -1
@@ -599,10 +601,10 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                 double v = U[kk * NU + 2 * i];
                 sk = SN[kk * M_ + i]; ck = CS[kk * M_ + i];
                 double a = -T * v * sk, b = T * v * ck;
-                r0 += 2 * P.q[0] * (x[3 * i] - XS[3 * i]) - ln[0];
-                r1 += 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]) - ln[1];
-                r2 += 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]) - (ln[2] + a * ln[0] + b * ln[1]);
-                if constexpr (FZ) { pk_cost(t, x, i); vn = v; ln0 = ln[0]; ln1 = ln[1]; }
+                r0 += 2 * P.q[0] * (x[3 * i] - XR(kk, 3 * i)) - ln[0];
+                r1 += 2 * P.q[1] * (x[3 * i + 1] - XR(kk, 3 * i + 1)) - ln[1];
+                r2 += 2 * P.q[2] * (x[3 * i + 2] - XR(kk, 3 * i + 2)) - (ln[2] + a * ln[0] + b * ln[1]);
+                if constexpr (FZ) { pk_cost(t, x, kk, i); vn = v; ln0 = ln[0]; ln1 = ln[1]; }
             }
             // Jx^T z : bounds, pairs (ascending partner), obstacles
             double j0, j1, j2 = 0.0;
@@ -729,7 +731,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             double *pk = gpack + (size_t)k * G::PACK;          // k == N: terminal block reuses the pack layout
             XTerms t;
             if (k >= 1) {
-                if (k < N) pk_cost(t, x, i);
+                if (k < N) pk_cost(t, x, k, i);
                 const int sb = k * NXB + (2 + THB) * i;
                 pk_bounds(t, x, i, ZXL[sb], ZXU[sb], ZXL[sb + 1], ZXU[sb + 1], THB ? ZXL[sb + 2] : 0.0, THB ? ZXU[sb + 2] : 0.0);
                 if (k <= N - 1) {
@@ -1494,9 +1496,9 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
                     l0 += n0 * znew + zz * (dx[3 * i] - n0 * nd);
                     l1 += n1 * znew + zz * (dx[3 * i + 1] - n1 * nd);
                 }
-                l0 -= 2 * P.q[0] * (x[3 * i] - XS[3 * i]) + 2 * P.q[0] * dx[3 * i];
-                l1 -= 2 * P.q[1] * (x[3 * i + 1] - XS[3 * i + 1]) + 2 * P.q[1] * dx[3 * i + 1];
-                l2 -= 2 * P.q[2] * (x[3 * i + 2] - XS[3 * i + 2]) + 2 * P.q[2] * dx[3 * i + 2];
+                l0 -= 2 * P.q[0] * (x[3 * i] - XR(k, 3 * i)) + 2 * P.q[0] * dx[3 * i];
+                l1 -= 2 * P.q[1] * (x[3 * i + 1] - XR(k, 3 * i + 1)) + 2 * P.q[1] * dx[3 * i + 1];
+                l2 -= 2 * P.q[2] * (x[3 * i + 2] - XR(k, 3 * i + 2)) + 2 * P.q[2] * dx[3 * i + 2];
                 const double *ln = LAM + (k + 1) * NX + 3 * i;
                 double v = U[k * NU + 2 * i], c = CS[k * M_ + i], s = SN[k * M_ + i];
                 double htt = pk_htt(v, ln[0], ln[1], c, s), hvt = pk_hvt(ln[0], ln[1], c, s);
@@ -1532,7 +1534,7 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
             int k = it / M_, i = it - k * M_;
             if (k >= 1) {
 #pragma unroll
-                for (int d = 0; d < 3; d++) dphi += 2 * P.q[d] * (X[k * NX + 3 * i + d] - XS[3 * i + d]) * DX[k * NX + 3 * i + d];
+                for (int d = 0; d < 3; d++) dphi += 2 * P.q[d] * (X[k * NX + 3 * i + d] - XR(k, 3 * i + d)) * DX[k * NX + 3 * i + d];
             }
 #pragma unroll
             for (int d = 0; d < 2; d++) { const int eu = k * NU + 2 * i + d; dphi += 2 * P.r[d] * U[eu] * DU[eu]; }
@@ -1660,22 +1662,23 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
         asm volatile("" : "+s"(Ne), "+s"(Ke));
         const int N1e = Ne + 1, MKe = M_ * Ke;
         const ColLayout<M_, THB> Le(Ne, Ke);
-        const double *Xe = sm + Le.X, *Ue = sm + Le.U, *LAMe = sm + Le.LAM, *SNe = sm + Le.SN, *CSe = sm + Le.CS, *XSe = sm + Le.XS;
+        const double *Xe = sm + Le.X, *Ue = sm + Le.U, *LAMe = sm + Le.LAM, *SNe = sm + Le.SN, *CSe = sm + Le.CS;
+        const PoseRows<TR> XRe(sm + Le.XS, R, inst);
         double *gde = DLL ? sm + Le.end : ws + inst * P.stride2 + P.oDUAL;
         const UArr zp{gde, Le.ZPp}, zo{gde, Le.ZO}, zul{gde, Le.ZUL}, zuu{gde, Le.ZUU}, zxl{gde, Le.ZXL}, zxu{gde, Le.ZXU};
         double *lg = P.lam_g ? P.lam_g + inst * (size_t)P.ng : nullptr;
         double *lp = P.lam_p ? P.lam_p + inst * (size_t)(2 * NX) : nullptr;
-        // initial block X_0 - x0: from stationarity in X_0 (the stage-0 pair / obstacle rows carry 0); lam_p = (the same, 2 Q sum_k (X_k - xs))
+        // initial block X_0 - x0: from stationarity in X_0 (the stage-0 pair / obstacle rows carry 0); lam_p = (the same, 2 Q sum_k (X_k - xs_k))
         for (int c = tid; c < NX; c += TPB) {
             const int i = c / 3, d = c - 3 * i;
             const double *ln = LAMe + NX + 3 * i;
             double a = ln[d];
             if (d == 2) { const double tv = P.T * Ue[2 * i]; a += (-tv * SNe[i]) * ln[0] + (tv * CSe[i]) * ln[1]; }
-            const double v = a - 2.0 * P.q[d] * (Xe[c] - XSe[c]);
+            const double v = a - 2.0 * P.q[d] * (Xe[c] - XRe(0, c));
             if (lg) lg[c] = v;
             if (lp) {
                 double s = 0.0;
-                for (int k = 0; k < Ne; k++) s += Xe[k * NX + c] - XSe[c];
+                for (int k = 0; k < Ne; k++) s += Xe[k * NX + c] - XRe(k, c);
                 lp[c] = v; lp[NX + c] = 2.0 * P.q[d] * s;
             }
         }
@@ -1702,6 +1705,30 @@ __global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_co
     if (tid == 0 && prof_out) for (int i = 0; i < 12; i++) atomicAdd((unsigned long long *)&prof_out[i], (unsigned long long)prof[i]);
 #endif
 }
+
+template <int M_, int THB, int DL, int TPBK = 64>
+__global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void solve_col_kernel(const KParams P, const double *__restrict__ p_in, const double *__restrict__ w0,
+                                                        double *__restrict__ w_out, double *__restrict__ obj_out,
+                                                        int32_t *__restrict__ status_out, int32_t *__restrict__ iters_out,
+                                                        double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
+{
+    const PoseRef none{nullptr, 0, 0};      // never read (PoseRows<0>)
+    solve_col_body<M_, THB, DL, TPBK, 0>(P, none, p_in, w0, w_out, obj_out, status_out, iters_out, kkt_out, ws, prof_out);
+}
+
+// The tracking solve (nmpc_solve_batch_ref, nmpc_step_batch_ref): the same body with the cost of stage k measured against row k of R.  A kernel
+// of its own name with the reference as its own argument: KParams and the plain kernel keep their layout.  Instantiated with the per-instance
+// obstacle field only (DL | NMPC_DL_OBS): a call without one reads the handle's device copy of the config's field (nmpc_api.cpp).
+template <int M_, int THB, int DL, int TPBK = 64>
+__global__ __launch_bounds__(TPBK, col_min_waves(M_, THB, DL & 3)) void track_col_kernel(const KParams P, const PoseRef R, const double *__restrict__ p_in,
+                                                        const double *__restrict__ w0, double *__restrict__ w_out, double *__restrict__ obj_out,
+                                                        int32_t *__restrict__ status_out, int32_t *__restrict__ iters_out,
+                                                        double *__restrict__ kkt_out, double *__restrict__ ws, long long *__restrict__ prof_out)
+{
+    static_assert((DL & NMPC_DL_OBS) != 0, "the tracking kernel reads the per-instance obstacle field");
+    solve_col_body<M_, THB, DL, TPBK, 1>(P, R, p_in, w0, w_out, obj_out, status_out, iters_out, kkt_out, ws, prof_out);
+}
+constexpr int NMPC_DL_TRACK = 8;    // bit of SolveVariant.flags (not of DL): the launch is track_col_kernel
 
 // LDS bytes of one instance of the column-per-lane kernel
 template <int M_, int THB> static size_t col_lds_bytes(const KParams &P, bool duals, int fl = 0)      // fl: 2 = + stage factors, 3 = + stage packs (see the kernel)
@@ -1738,8 +1765,10 @@ template <int M_, int THB> static int col_factor_mode(const KParams &P)
     return col_lds_bytes<M_, THB>(P, true, NMPC_COL_FL_MODE) <= NMPC_COL_FL_BYTES ? NMPC_COL_FL_MODE : 0;
 }
 
-// OBS = 1: the instantiations of the per-instance obstacle field (P.ofield), in the same shapes and data layouts as the plain ones
+// OBS = 1: the instantiations of the per-instance obstacle field (P.ofield), in the same shapes and data layouts as the plain ones;
+// OBS = 2: the tracking kernel's, which exist with that field only, in the same shapes and data layouts again
 template <int M_, int OBS> struct ColInst {
+    static constexpr int TR = OBS == 2 ? NMPC_DL_TRACK : 0;
     static constexpr int OB = OBS ? NMPC_DL_OBS : 0;
     static constexpr int DLmax = (M_ <= NMPC_COL_DL_MAXM) ? 1 : 0;
     // latency shape (two wavefronts per instance): slacks and duals in LDS up to six robots — occupancy is not what a launch that lasts as
@@ -1759,10 +1788,16 @@ template <int M_, int THB, int OBS> static SolveVariant select3_mt(const KParams
     const int fl = (!lat && dl) ? col_factor_mode<M_, THB>(P) : 0;
     const size_t lds = col_lds_bytes<M_, THB>(P, dl, fl);
     if (shape == 2 && I::TPB4 == 128) shape = 1;
-    if (shape == 2) return SolveVariant{KERN_COL, M_, THB, I::DLlat | I::OB, I::TPB4, lds};
-    if (lat) return SolveVariant{KERN_COL, M_, THB, I::DLlat | I::OB, 128, lds};
-    if (fl) return SolveVariant{KERN_COL, M_, THB, I::DLmax * I::FLM | I::OB, 64, lds};
-    return SolveVariant{KERN_COL, M_, THB, (dl ? I::DLmax : 0) | I::OB, 64, lds};
+    if (shape == 2) return SolveVariant{KERN_COL, M_, THB, I::DLlat | I::OB | I::TR, I::TPB4, lds};
+    if (lat) return SolveVariant{KERN_COL, M_, THB, I::DLlat | I::OB | I::TR, 128, lds};
+    if (fl) return SolveVariant{KERN_COL, M_, THB, I::DLmax * I::FLM | I::OB | I::TR, 64, lds};
+    return SolveVariant{KERN_COL, M_, THB, (dl ? I::DLmax : 0) | I::OB | I::TR, 64, lds};
+}
+// the kernel of an instantiation: solve_col_kernel, or (TR) track_col_kernel
+template <int TR, int M_, int THB, int DL, int TPB> static constexpr auto col_kernel()
+{
+    if constexpr (TR) return &track_col_kernel<M_, THB, DL, TPB>;
+    else return &solve_col_kernel<M_, THB, DL, TPB>;
 }
 // launches the instantiation whose template arguments are v's
 template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
@@ -1770,22 +1805,25 @@ template <int M_, int THB, int OBS> static hipError_t launch3_mt(const KParams &
     using I = ColInst<M_, OBS>;
     const size_t lds = v.lds;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = (v.threads == I::TPB4 && v.flags == (I::DLlat | I::OB)) ? solve_col_kernel<M_, THB, I::DLlat | I::OB, I::TPB4>
-                : (v.threads == 128 && v.flags == (I::DLlat | I::OB)) ? solve_col_kernel<M_, THB, I::DLlat | I::OB, 128>
-                : (v.threads == 64 && v.flags == (I::DLmax * I::FLM | I::OB)) ? solve_col_kernel<M_, THB, I::DLmax * I::FLM | I::OB, 64>
-                : (v.threads == 64 && v.flags == (I::DLmax | I::OB)) ? solve_col_kernel<M_, THB, I::DLmax | I::OB, 64>
-                : (v.threads == 64 && v.flags == I::OB) ? solve_col_kernel<M_, THB, I::OB, 64> : nullptr;
+    constexpr int TR = I::TR != 0;
+    const int fl = v.flags ^ I::TR;      // the kernel's DL
+    auto kern = (v.threads == I::TPB4 && fl == (I::DLlat | I::OB)) ? col_kernel<TR, M_, THB, I::DLlat | I::OB, I::TPB4>()
+                : (v.threads == 128 && fl == (I::DLlat | I::OB)) ? col_kernel<TR, M_, THB, I::DLlat | I::OB, 128>()
+                : (v.threads == 64 && fl == (I::DLmax * I::FLM | I::OB)) ? col_kernel<TR, M_, THB, I::DLmax * I::FLM | I::OB, 64>()
+                : (v.threads == 64 && fl == (I::DLmax | I::OB)) ? col_kernel<TR, M_, THB, I::DLmax | I::OB, 64>()
+                : (v.threads == 64 && fl == I::OB) ? col_kernel<TR, M_, THB, I::OB, 64>() : nullptr;
     if (!kern) return hipErrorInvalidValue;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(v.threads), lds, st, P, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws, a.prof);
+    if constexpr (TR) hipLaunchKernelGGL(kern, dim3(B), dim3(v.threads), lds, st, P, a.ref, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws, a.prof);
+    else hipLaunchKernelGGL(kern, dim3(B), dim3(v.threads), lds, st, P, a.p, a.w0, a.w_out, a.obj, a.status, a.iters, a.kkt, a.ws, a.prof);
     return hipGetLastError();
 }
 
-// One compile unit of the kernel: the team sizes LO..HI with (OBS = 1) or without the per-instance obstacle field.  The ten team sizes take
-// ~350 s per field flag in one translation unit, so build.py compiles this source once per unit (-DNMPC_COL_UNIT=LO,HI,OBS: one object each,
+// One compile unit of the kernel: the team sizes LO..HI with (OBS = 1) or without the per-instance obstacle field, or (OBS = 2) of the
+// tracking kernel.  The ten team sizes take ~350 s per such flag in one translation unit, so build.py compiles this source once per unit (-DNMPC_COL_UNIT=LO,HI,OBS: one object each,
 // spread over the cores); the unit built with -DNMPC_COL_ENTRY carries the host entry points below as well.  Without NMPC_COL_UNIT (variant
 // builds, NMPC_COL_ONLY_M) everything is in this one object.
 template <int LO, int HI, int OBS> hipError_t launch_col_unit(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
@@ -1800,9 +1838,9 @@ template <int LO, int HI, int OBS> hipError_t launch_col_unit(const KParams &P, 
 #if !defined(NMPC_COL_UNIT) || defined(NMPC_COL_ENTRY)
 // the units: the table COL_UNITS of build.py
 #ifdef NMPC_COL_ONLY_M
-#define NMPC_COL_UNITS(U) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 0) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 1)
+#define NMPC_COL_UNITS(U) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 0) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 1) U(NMPC_COL_ONLY_M, NMPC_COL_ONLY_M, 2)
 #else
-#define NMPC_COL_UNITS(U) U(1, 5, 0) U(6, 8, 0) U(9, 10, 0) U(1, 5, 1) U(6, 8, 1) U(9, 10, 1)
+#define NMPC_COL_UNITS(U) U(1, 5, 0) U(6, 8, 0) U(9, 10, 0) U(1, 5, 1) U(6, 8, 1) U(9, 10, 1) U(1, 5, 2) U(6, 8, 2) U(9, 10, 2)
 #endif
 #ifdef NMPC_COL_UNIT      // instantiated in the unit's own object
 #define U(LO, HI, OBS) extern template hipError_t launch_col_unit<LO, HI, OBS>(const KParams &, const SolveVariant &, int, const SolveArgs &, hipStream_t);
@@ -1813,7 +1851,7 @@ NMPC_COL_UNITS(U)
 hipError_t launch_solve_col(const KParams &P, const SolveVariant &v, int B, const SolveArgs &a, hipStream_t st)
 {
     if (v.kernel != KERN_COL) return hipErrorInvalidValue;
-#define U(LO, HI, OBS) if (v.m >= LO && v.m <= HI && ((v.flags & NMPC_DL_OBS) != 0) == (OBS != 0)) return launch_col_unit<LO, HI, OBS>(P, v, B, a, st);
+#define U(LO, HI, OBS) if (v.m >= LO && v.m <= HI && ((v.flags & NMPC_DL_TRACK) ? 2 : (v.flags & NMPC_DL_OBS) ? 1 : 0) == OBS) return launch_col_unit<LO, HI, OBS>(P, v, B, a, st);
     NMPC_COL_UNITS(U)
 #undef U
     return hipErrorInvalidValue;
@@ -1824,6 +1862,16 @@ bool select_solve_col(const KParams &P, int m, int shape, bool ofield, SolveVari
     return for_team_size(m, false, [&](auto M) {
         constexpr int M_ = decltype(M)::value;
         *v = ofield ? (P.thb ? select3_mt<M_, 1, 1>(P, shape) : select3_mt<M_, 0, 1>(P, shape)) : (P.thb ? select3_mt<M_, 1, 0>(P, shape) : select3_mt<M_, 0, 0>(P, shape));
+        return true;
+    });
+}
+
+// the tracking kernel's instantiation of the given shape: the field kernel's, in the same LDS (the reference's rows stay in device memory)
+bool select_track_col(const KParams &P, int m, int shape, SolveVariant *v)
+{
+    return for_team_size(m, false, [&](auto M) {
+        constexpr int M_ = decltype(M)::value;
+        *v = P.thb ? select3_mt<M_, 1, 2>(P, shape) : select3_mt<M_, 0, 2>(P, shape);
         return true;
     });
 }

@@ -99,6 +99,28 @@ template <int OS> struct ObsField {
     }
 };
 
+// ---- the pose reference of the cost: component c (0 .. NX-1) of the pose that the cost of stage k measures X_k against.  Every such read of
+// the column kernel goes through here; where the row comes from is a compile-time choice of the instantiation, never a run-time branch:
+//   TR = 0  the goal, the xs half of p, staged once as XS [NX] in LDS and the same for every stage (nmpc_solve_batch and its kin);
+//   TR = 1  row k of the instance's reference R.ptr [B][S][NX] in device memory (the *_ref solve calls, track_col_kernel): wave-uniform base,
+//           32-bit element offset (saddr addressing, as ObsField<1>); the stage stride is 0 for a single row (S = 1).  XS is never loaded.
+template <int TR> struct PoseRows {
+    const double *XS;     // TR = 0: [NX] in LDS
+    const PoseRef &R;     // TR = 1: the kernel argument
+    const double *f;      //         the instance's [S][NX]
+    __device__ __forceinline__ PoseRows(const double *XS_, const PoseRef &R_, size_t inst) : XS(XS_), R(R_), f(nullptr)
+    {
+        if constexpr (TR != 0) f = R_.ptr + inst * (size_t)R_.istride;
+    }
+    __device__ __forceinline__ double operator()(int k, int c) const
+    {
+        if constexpr (TR != 0)
+            return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(f) + (size_t)((uint32_t)(k * R.sstride + c) * 8u));
+        else
+            return XS[c];
+    }
+};
+
 // ---- single evaluation points.  Constraint values, slack steps and defects are recomputed at several places of an
 // iteration (Newton right-hand side, step-size rule, multiplier recursion, update).  With sigma = z/s up to 1e13 a
 // last-bit difference between two sites (e.g. a differently contracted a*b+c) shows up as 1e-7 in the dual residual, so

@@ -178,7 +178,7 @@ class NmpcSolver:
             raise ValueError(f"order must have shape ({B},)")
         return od
 
-    def solve_batch(self, p, w0, want_fg: bool = False, order=None, obstacles=None, want_duals: bool = False):
+    def solve_batch(self, p, w0, want_fg: bool = False, order=None, obstacles=None, want_duals: bool = False, reference=None):
         """p [B, 2 n_x], w0 [B, n_var] (torch cuda / numpy) -> dict of torch cuda tensors.
 
         order: optional permutation of range(B) (dispatch-order hint, nmpc_solve_batch_ordered): workgroup g solves instance
@@ -186,13 +186,17 @@ class NmpcSolver:
         obstacles: optional per-instance obstacle field (nmpc_solve_batch_obs), [B, K, 3] static or [B, N, K, 3] per stage (entry k: the
         obstacles at the time of X_k), K = len(cfg.obstacles); the config's coordinates are then not used.
         want_duals: also return the multipliers of the returned point, lam_g [B, n_g], lam_x [B, n_var], lam_p [B, n_p], in CasADi's layout
-        and sign (nmpc_solve_batch_duals, include/nmpc.h); the other results do not depend on it."""
+        and sign (nmpc_solve_batch_duals, include/nmpc.h); the other results do not depend on it.
+        reference: optional pose reference of the cost (nmpc_solve_batch_ref: trajectory tracking), [B, n_x] or [B, N, n_x] (row k: where X_k
+        should be); the xs half of p is then not read.  Composes with order, obstacles, want_duals and want_fg (f and g then come from
+        eval_batch(reference=)).  Needs a handle on the column-per-lane kernel (duals_supported())."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w0 = self._dev(w0, (B, self.n_var))
         if B > self.max_batch:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
         ob = self._obstacles(obstacles, B) if obstacles is not None else None
+        rf = self._reference(reference, B) if reference is not None else None
         w = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
         obj = torch.empty(B, dtype=torch.float64, device=self.device)
         kkt = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -201,7 +205,15 @@ class NmpcSolver:
         lam = {}
         with torch.cuda.device(self.device):
             od = self._order(order, B)
-            if want_duals:
+            if rf is not None:
+                cd = None
+                if want_duals:
+                    lam, cd = self._duals(B)
+                _lib.check(self.lib.nmpc_solve_batch_ref(self._h, B, p.data_ptr(), rf[0].data_ptr(), rf[1], ob[0].data_ptr() if ob is not None else None,
+                                                         ob[1] if ob is not None else 0, w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(),
+                                                         iters.data_ptr(), kkt.data_ptr(), od.data_ptr() if od is not None else None,
+                                                         C.byref(cd) if cd is not None else None, self._stream()), "nmpc_solve_batch_ref")
+            elif want_duals:
                 lam, cd = self._duals(B)
                 _lib.check(self.lib.nmpc_solve_batch_duals(self._h, B, p.data_ptr(), ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0,
                                                            w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
@@ -218,17 +230,19 @@ class NmpcSolver:
                                                              iters.data_ptr(), kkt.data_ptr(), od.data_ptr(), self._stream()), "nmpc_solve_batch_ordered")
         out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt, **lam)
         if want_fg:
-            f, g = self.eval_batch(p, w, obstacles=ob[0] if ob is not None else None)
+            f, g = self.eval_batch(p, w, obstacles=ob[0] if ob is not None else None, reference=rf[0] if rf is not None else None)
             out["f"], out["g"] = f, g
         return out
 
-    def step_batch(self, p, w, order=None, obstacles=None, want_duals: bool = False):
+    def step_batch(self, p, w, order=None, obstacles=None, want_duals: bool = False, reference=None):
         """One control period on the device (nmpc_step_batch): solve from the guess w, then IN PLACE w <- shifted solution and
         p[:, :n_x] <- x0 + T f(x0, u_0); `order` [B] int32 device tensor (in: dispatch order of this period, out: the order for the
         next one, sorted by this period's iteration counts, longest first) or None.  p and w must be contiguous float64 device
         tensors owned by the caller (they are modified).  Returns sol['x'] of this period and the per-instance outputs.
         obstacles: optional per-instance obstacle field of this period (nmpc_step_batch_obs), as in solve_batch.
-        want_duals: also return lam_g, lam_x, lam_p of this period's solution (nmpc_step_batch_duals), as in solve_batch."""
+        want_duals: also return lam_g, lam_x, lam_p of this period's solution (nmpc_step_batch_duals), as in solve_batch.
+        reference: optional pose reference of this period's window (nmpc_step_batch_ref), as in solve_batch; it is not written: the caller
+        supplies the next period's window of its path."""
         torch = self.torch
         B = p.shape[0]
         if not (torch.is_tensor(p) and torch.is_tensor(w) and p.is_cuda and w.is_cuda and p.dtype == torch.float64 and w.dtype == torch.float64
@@ -242,7 +256,15 @@ class NmpcSolver:
         x = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
         obj = torch.empty(B, dtype=torch.float64, device=self.device); kkt = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device); iters = torch.empty(B, dtype=torch.int32, device=self.device)
+        rf = self._reference(reference, B) if reference is not None else None
         with torch.cuda.device(self.device):
+            if rf is not None:
+                lam, cd = self._duals(B) if want_duals else ({}, None)
+                _lib.check(self.lib.nmpc_step_batch_ref(self._h, B, p.data_ptr(), w.data_ptr(), x.data_ptr(), rf[0].data_ptr(), rf[1],
+                                                        ob[0].data_ptr() if ob is not None else None, ob[1] if ob is not None else 0, obj.data_ptr(),
+                                                        status.data_ptr(), iters.data_ptr(), kkt.data_ptr(), order.data_ptr() if order is not None else None,
+                                                        C.byref(cd) if cd is not None else None, self._stream()), "nmpc_step_batch_ref")
+                return dict(x=x, f=obj, status=status, iters=iters, kkt=kkt, order=order, **lam)
             if want_duals:
                 lam, cd = self._duals(B)
                 _lib.check(self.lib.nmpc_step_batch_duals(self._h, B, p.data_ptr(), w.data_ptr(), x.data_ptr(), ob[0].data_ptr() if ob is not None else None,
@@ -612,10 +634,14 @@ class PipelinedSolver:
         w0 = sol._dev(w0, (p.shape[0], sol.n_var))
         if kw.get("obstacles") is not None:
             kw["obstacles"] = sol._obstacles(kw["obstacles"], p.shape[0])[0]      # the field too: [B, S, K, 3] on the device
+        if kw.get("reference") is not None:
+            kw["reference"] = sol._reference(kw["reference"], p.shape[0])[0]      # and the pose reference: [B, S, n_x] on the device
         st.wait_stream(torch.cuda.current_stream(self.device))
         p.record_stream(st); w0.record_stream(st)            # the caller may drop its references at once: the allocator must not hand the inputs out again before the solve has read them
         if kw.get("obstacles") is not None:
             kw["obstacles"].record_stream(st)
+        if kw.get("reference") is not None:
+            kw["reference"].record_stream(st)
         with torch.cuda.stream(st):
             r = sol.solve_batch(p, w0, **kw)
             ev = torch.cuda.Event()
