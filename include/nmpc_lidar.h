@@ -66,6 +66,52 @@ int32_t nmpc_lidar_solve_batch(nmpc_lidar_handle_t *h, int32_t B, const double *
 /* f (V4:135-136) and g [B][n_g] = [gx; gd] (V4:151) at w: backs sol['f'] / sol['g'] */
 int32_t nmpc_lidar_eval_batch(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w, double *f, double *g, void *stream);
 
+/*
+ * The solver's own multipliers: sol['lam_g'], sol['lam_x'], sol['lam_p'] of the CasADi call (V4:245), and a KKT certificate of any
+ * (w, lam_g, lam_x) for a whole batch on the device.
+ *
+ * Convention (CasADi's, as in nmpc.h): L = f + lam_g' g + lam_x' w + lam_p' p with grad_w L = 0 and grad_p L = 0 at a solution; a multiplier
+ * is <= 0 on an active lower bound and >= 0 on an active upper bound.  The layouts of g, w and p are those of nmpc_lidar_eval_batch.
+ *   lam_g [B][n_g]   rows of gx and gd of stages 1..N: the solver's multiplier of that row, with the sign of that g, in the order "all gx
+ *                    rows, then all gd rows";
+ *                    stage-0 rows X_0[:3] - p[:3] and d_0 - scan: from stationarity in all 3 + R components of X_0,
+ *                    -(d f / d X_0 + sum over the rows of stages >= 1 of lam_g,row d g_row / d X_0): for the pose the cost and the defect of
+ *                    stage 0 and every gd row of stages 1..N through the lidar points pObs(X_0); for d_0m the cost term -2 lw / d^3 of stage 0 and
+ *                    the gd rows of ray m.  d|a|/da = sgn(a) with sgn(0) = 0.
+ *   lam_x [B][n_var] (dual of the upper bound) - (dual of the lower bound), entry by entry in the caller's index of w and for whatever bound
+ *                    pattern lbx / ubx hold; 0 where an entry has no finite bound; X_0: 0.
+ *   lam_p [B][6+2R]  -(d f / d p)' - (d g / d p)' lam_g: the x0 part equals lam_g[0:3] (bit for bit), the xs part is 2 Q sum_{k<N} (X_k - xs), the
+ *                    scan part equals lam_g of the stage-0 gd rows (bit for bit), the ray-angle part comes through pObs.  So d f* / d p = -lam_p:
+ *                    the sensitivity of the optimal cost to the measured pose, the goal, the scan and the ray angles.
+ * The sums over the horizon run in a fixed order (per lane over its stages, then over the wave): the same inputs give the same bits.
+ * By status: 0: the multipliers of the returned point, for which the solve's own optimality test held; 1 / 4: those of the last iterate;
+ * 2: whatever the iterate holds, possibly non-finite; 3 (infeasible at stage 0, the return before the iteration): all three rows are zero.
+ *
+ * nmpc_lidar_solve_batch_duals is nmpc_lidar_solve_batch (same launch choice, same kernel) followed on the same stream by one launch that
+ * reads the multipliers out of the handle's workspace.  Each member of *duals is a device pointer or NULL (not written); duals == NULL, or
+ * all three members NULL, is exactly the plain call; w_out, obj, status, iters, kkt never depend on duals.  Argument errors: those of
+ * nmpc_lidar_solve_batch.
+ *
+ * nmpc_lidar_kkt_batch evaluates, for given w [B][n_var], lam_g [B][n_g], lam_x [B][n_var] (a solve's output or a caller's own),
+ *   grad_lag [B][n_var] = grad f + J' lam_g + lam_x   (written when not NULL; all of X_0 included, the stage-0 rows enter with the multipliers
+ *                                                      given) and
+ *   res [B][6] = (stat, eq, ineq, bnd, compl, sign), the index meaning of nmpc_kkt_batch:
+ *     stat   inf-norm of grad_lag
+ *     eq     largest |g_i|
+ *     ineq   0.0 always: every row of this NLP is an equality
+ *     bnd    largest violation of a variable bound lbx / ubx (stage 0 included), at least 0
+ *     compl  largest of max(-lam_x_j, 0) (w_j - lbx_j) and max(lam_x_j, 0) (ubx_j - w_j) over the finite variable bounds, at least 0
+ *     sign   largest lam_x_j of the wrong sign at a one-sided bound (positive with a lower bound only, negative with an upper bound only), at
+ *            least 0
+ *   with IEEE divisions (it does not share the solve kernel's fast division).  A NaN in the inputs reaches the numbers it enters.  Works on
+ *   every handle and for any B (it uses no workspace), like nmpc_lidar_eval_batch.  NMPC_E_ARG for a null handle, B < 0, or null p, w, lam_g,
+ *   lam_x or res with B > 0.
+ */
+int32_t nmpc_lidar_solve_batch_duals(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj,
+                                     int32_t *status, int32_t *iters, double *kkt, const nmpc_duals_t *duals, void *stream);
+int32_t nmpc_lidar_kkt_batch(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w, const double *lam_g, const double *lam_x,
+                             double *res /* [B][6] */, double *grad_lag /* [B][n_var] or NULL */, void *stream);
+
 /* warm-start shuffle of V4:258-270: U rows drop first / repeat last; X rows [X_1..X_N; X_{N-1}] */
 int32_t nmpc_lidar_shift_batch(nmpc_lidar_handle_t *h, int32_t B, const double *w_in, double *w_next, void *stream);
 

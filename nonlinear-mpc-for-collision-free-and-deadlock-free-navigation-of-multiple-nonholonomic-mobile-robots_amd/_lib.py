@@ -19,7 +19,8 @@ STATUS_NAMES = {0: "Solve_Succeeded", 1: "Maximum_Iterations_Exceeded", 2: "Erro
 ERRORS = {-1: "NMPC_E_ARG", -2: "NMPC_E_UNSUPPORTED", -3: "NMPC_E_HIP", -4: "NMPC_E_NOMEM"}
 
 LIDAR_EXPORTS = ["nmpc_lidar_n_var", "nmpc_lidar_n_g", "nmpc_lidar_n_p", "nmpc_lidar_create", "nmpc_lidar_destroy", "nmpc_lidar_solve_batch",
-                 "nmpc_lidar_eval_batch", "nmpc_lidar_shift_batch", "nmpc_lidar_scan_batch", "nmpc_lidar_plant_batch"]
+                 "nmpc_lidar_eval_batch", "nmpc_lidar_shift_batch", "nmpc_lidar_scan_batch", "nmpc_lidar_plant_batch", "nmpc_lidar_solve_batch_duals",
+                 "nmpc_lidar_kkt_batch"]
 DEBUG_EXPORTS = ["nmpc_debug_profile", "nmpc_debug_trace", "nmpc_debug_trace2", "nmpc_debug_workspace", "nmpc_debug_variant", "nmpc_debug_variant_of_config", "nmpc_debug_track_variant_of_config", "nmpc_debug_lidar_variant"]      # include/nmpc_debug.h
 QUERY_KERNEL_FOR_BATCH, QUERY_WORKSPACE_BYTES, QUERY_LDS_BYTES, QUERY_MAX_BATCH, QUERY_KERNEL_FOR_ORDERED_BATCH = 1, 2, 3, 4, 5      # NMPC_QUERY_* of include/nmpc.h
 QUERY_SENS_DIRS_PER_PASS = 6
@@ -133,6 +134,8 @@ def load():
     L.nmpc_lidar_create.argtypes = [lp, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, C.POINTER(vp)]; L.nmpc_lidar_create.restype = i32
     L.nmpc_lidar_destroy.argtypes = [vp]; L.nmpc_lidar_destroy.restype = i32
     L.nmpc_lidar_solve_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_lidar_solve_batch.restype = i32
+    L.nmpc_lidar_solve_batch_duals.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, dp, vp]; L.nmpc_lidar_solve_batch_duals.restype = i32
+    L.nmpc_lidar_kkt_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]; L.nmpc_lidar_kkt_batch.restype = i32
     L.nmpc_lidar_eval_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]; L.nmpc_lidar_eval_batch.restype = i32
     L.nmpc_lidar_shift_batch.argtypes = [vp, i32, vp, vp, vp]; L.nmpc_lidar_shift_batch.restype = i32
     L.nmpc_lidar_scan_batch.argtypes = [C.c_int64, i32, i32, vp, vp, C.c_double, vp, vp]; L.nmpc_lidar_scan_batch.restype = i32

@@ -318,10 +318,13 @@ class LidarEpisodeResult:
     total_solves: int
     mean_iters_by_step: "np.ndarray"
     poses: Optional["np.ndarray"] = None     # [steps+1, B, 3] when keep_poses
+    worst_stat: Optional["np.ndarray"] = None     # [B] when certify: largest stationarity residual of the solver's own primal-dual point over the periods with status 0
+    worst_eq: Optional["np.ndarray"] = None       # [B] ... largest equality residual
+    worst_compl: Optional["np.ndarray"] = None    # [B] ... largest complementarity product
 
 
 def simulate_lidar_closed_loop(solver, pose0, goals, world, max_steps: int, arrive_tol: float = 0.2, scan_max: float = 3.5,
-                               keep_poses: bool = False) -> LidarEpisodeResult:
+                               keep_poses: bool = False, certify: bool = False) -> LidarEpisodeResult:
     """The main loop of AllScripts/obs_avoid_static_first_scenario_v4.py (V4:209-300) for B simulated robots at once.
 
     Per robot and control period (file:line of the reference):
@@ -333,7 +336,10 @@ def simulate_lidar_closed_loop(solver, pose0, goals, world, max_steps: int, arri
       ne = ||Xr - xs|| < 0.2 -> next goal; past the last: arrived   V4:281-291 (goal_idx, ng)
       x0[3:] = Scan ; x0[:3] = Xr                                V4:296-297
     pose0 [B,3]; goals [B,G,3] (or [B,3]); world [B,K,3] circular obstacles (ox, oy, radius).  As in the script a non-converged solve's control is
-    applied as returned (counted in failed_solves); a robot that has arrived stays where it is and keeps solving its fixed point."""
+    applied as returned (counted in failed_solves); a robot that has arrived stays where it is and keeps solving its fixed point.
+    certify: every period's solve also returns its multipliers (solve_batch(want_duals=True)) and one kkt_batch call certifies the primal-dual
+    point on the device; worst_stat / worst_eq / worst_compl [B] are the maxima over the periods in which the robot's solve returned status 0
+    (0 when there was none).  The loop itself and every other result are those of certify=False, bit for bit."""
     torch = solver.torch
     cfg = solver.cfg
     dev = solver.device
@@ -366,12 +372,16 @@ def simulate_lidar_closed_loop(solver, pose0, goals, world, max_steps: int, arri
     poses = [pose.clone()] if keep_poses else None
     its = []
     failed = total = steps = 0
+    worst = torch.zeros((B, 3), dtype=torch.float64, device=dev)      # certify: (stat, eq, compl)
     for step in range(max_steps):
         if bool(arrived.all()):
             break
         xs = g[ar, gi]
         p = torch.cat([pose, xs, scan, ang[None, :].expand(B, -1)], dim=1).contiguous()
-        r = solver.solve_batch(p, w)
+        r = solver.solve_batch(p, w, want_duals=certify)
+        if certify:
+            res = solver.kkt_batch(p, r["x"], r["lam_g"], r["lam_x"])
+            worst = torch.where((r["status"] == 0)[:, None], torch.maximum(worst, res[:, [0, 1, 4]]), worst)
         total += B
         failed += int((r["status"] != 0).sum())
         its.append(r["iters"].double().mean())
@@ -394,4 +404,5 @@ def simulate_lidar_closed_loop(solver, pose0, goals, world, max_steps: int, arri
     return LidarEpisodeResult(steps=steps, arrived=arrived.cpu().numpy(), arrival_step=arrival.cpu().numpy(), goals_reached=(gi + arrived.long()).cpu().numpy(),
                               min_clearance=clear.cpu().numpy(), final_error=err.cpu().numpy(), failed_solves=failed, total_solves=total,
                               mean_iters_by_step=torch.stack(its).cpu().numpy() if its else np.zeros(0),
-                              poses=torch.stack(poses).cpu().numpy() if keep_poses else None)
+                              poses=torch.stack(poses).cpu().numpy() if keep_poses else None,
+                              **(dict(zip(("worst_stat", "worst_eq", "worst_compl"), worst.cpu().numpy().T.copy())) if certify else {}))

@@ -966,6 +966,207 @@ __global__ __launch_bounds__(64) void lidar_eval_kernel(const LParams P, int B, 
     if (f_out && lane == 0) f_out[b] = fs;
 }
 
+// ---- multipliers and KKT certificate (include/nmpc_lidar.h: L = f + lam_g' g + lam_x' w + lam_p' p).  Both kernels below: one wavefront per
+// instance, lane = stage (+64, ...) as lidar_eval_kernel, IEEE divisions (no qdiv: a certificate does not share the solver's shortcuts), every
+// sum over the horizon per lane over its stages and then the wave reduction of nmpc_wave.h: the same inputs give the same bits.
+__device__ __forceinline__ void nan_max(double &a, double v) { a = (v > a || v != v) ? v : a; }      // a starts at 0: the positive part; fmax would drop a NaN
+__device__ __forceinline__ double wave_nan_max(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) nan_max(v, __shfl_xor(v, o));
+    return uniform_f64(v);
+}
+// lidar points of stage 0 from the stage-0 variables X0 = (x, y, theta, d_1..d_R) (V4:114-118) into SP [R][2]
+__device__ __forceinline__ void lidar_points(int lane, int R, const double *X0, const double *pp, double *SP)
+{
+    for (int m = lane; m < R; m += 64) {
+        double s, c;
+        sincos(X0[2] + pp[6 + R + m], &s, &c);
+        SP[2 * m] = X0[0] + X0[3 + m] * c; SP[2 * m + 1] = X0[1] + X0[3 + m] * s;
+    }
+    __syncthreads();
+}
+// What stage k < N puts on its own pose in the gradient of L: the cost and the defect row of stage k + 1 with multiplier (l0, l1, l2)
+__device__ __forceinline__ void stage_pose_terms(const LParams &P, const double *pp, double x, double y, double t, double u0, double s, double c, double l0, double l1,
+                                                 double l2, double &f0, double &f1, double &f2)
+{
+    f0 = 2.0 * P.q[0] * (x - pp[3]) - l0; f1 = 2.0 * P.q[1] * (y - pp[4]) - l1;
+    f2 = 2.0 * P.q[2] * (t - pp[5]) - l2 + P.T * u0 * (s * l0 - c * l1);
+}
+// What the gd rows of ray m, stages 1..N, put on X_0 through the lidar point pObs_m(X_0): Sx = sum_k eta_km sgn(x_k - pox), Sy likewise.  Then
+// d L / d (x_0, y_0) += (Sx, Sy), d L / d theta_0 and d L / d (ray angle m) += tq = d_0m (Sy cos - Sx sin), d L / d d_0m += td = Sx cos + Sy sin.
+struct RayTerms { double Sx, Sy, tq, td; };
+template <class Eta> __device__ __forceinline__ RayTerms ray_terms(int lane, int N, int R, int ns, const double *X, const double *pp, const double *SP, int m, Eta eta)
+{
+    double ax = 0.0, ay = 0.0;
+    for (int k = 1 + lane; k <= N; k += 64) {
+        const double e = eta(k, m);
+        ax += e * sgn(X[(size_t)k * ns] - SP[2 * m]); ay += e * sgn(X[(size_t)k * ns + 1] - SP[2 * m + 1]);
+    }
+    RayTerms r;
+    r.Sx = wsum(ax); r.Sy = wsum(ay);
+    double s, c;
+    sincos(X[2] + pp[6 + R + m], &s, &c);
+    r.tq = X[3 + m] * (r.Sy * c - r.Sx * s); r.td = r.Sx * c + r.Sy * s;
+    return r;
+}
+
+// The multipliers the interior-point loop left in the instance's workspace slot, in the caller's layout and sign, completed by the stage-0 rows
+// (stationarity in X_0) and lam_p.  Launched behind the solve kernel on its stream; reads the slot and w_sol, never the status: an instance
+// infeasible at stage 0 (the solve kernel's own test) gets zeros, its slot holds an earlier solve's values.
+__global__ __launch_bounds__(64) void lidar_duals_kernel(const LParams P, int B, const double *__restrict__ p_in, const double *__restrict__ w_sol,
+                                                          const double *__restrict__ ws, double *__restrict__ lam_g, double *__restrict__ lam_x,
+                                                          double *__restrict__ lam_p)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const int N = P.N, Nc = P.Nc, R = P.R, ns = P.ns, NP1 = N + 1;
+    const double *X = w_sol + (size_t)b * P.nvar, *U = X + (size_t)NP1 * ns, *pp = p_in + (size_t)b * P.np, *wsb = ws + (size_t)b * (size_t)P.total;
+    double *lg = lam_g ? lam_g + (size_t)b * P.ng : nullptr, *lgd = lg ? lg + 3 * NP1 : nullptr, *lx = lam_x ? lam_x + (size_t)b * P.nvar : nullptr,
+           *lp = lam_p ? lam_p + (size_t)b * P.np : nullptr;
+    __shared__ double SP[2 * NMPC_LIDAR_MAX_RAYS];
+    {   // the pinned stage-0 variables against their own bounds: the comparisons of the solve kernel
+        double bad = 0.0;
+        for (int c = lane; c < ns; c += 64) { double v = (c < 3) ? pp[c] : pp[6 + (c - 3)]; if (v < P.lb0[c] || v > P.ub0[c]) bad = 1.0; }
+        if (wmax(bad) > 0.0) {
+            if (lg) for (int e = lane; e < P.ng; e += 64) lg[e] = 0.0;
+            if (lx) for (int e = lane; e < P.nvar; e += 64) lx[e] = 0.0;
+            if (lp) for (int e = lane; e < P.np; e += 64) lp[e] = 0.0;
+            return;
+        }
+    }
+    lidar_points(lane, R, X, pp, SP);
+    auto lam = [&](int k, int i) { return wsb[P.olam + (size_t)i * N + (k - 1)]; };      // pose rows [3][N], stages 1..N
+    auto eta = [&](int k, int m) { return wsb[P.oeta + (size_t)m * N + (k - 1)]; };      // distance rows [R][N]
+    double xs0 = 0.0, xs1 = 0.0, xs2 = 0.0;
+    for (int k = lane; k <= N; k += 64) {
+        const double *v = X + (size_t)k * ns;
+        if (k < N) { xs0 += v[0] - pp[3]; xs1 += v[1] - pp[4]; xs2 += v[2] - pp[5]; }
+        if (lg && k >= 1) {
+            for (int i = 0; i < 3; i++) lg[3 * k + i] = lam(k, i);
+            for (int m = 0; m < R; m++) lgd[R * k + m] = eta(k, m);
+        }
+        if (lx) for (int c = 0; c < ns; c++) lx[(size_t)k * ns + c] = k ? wsb[P.oZU + (size_t)c * NP1 + k] - wsb[P.oZL + (size_t)c * NP1 + k] : 0.0;
+    }
+    if (lx) for (int e = lane; e < 2 * Nc; e += 64) lx[(size_t)NP1 * ns + e] = wsb[P.oZUu + e] - wsb[P.oZLu + e];
+    xs0 = wsum(xs0); xs1 = wsum(xs1); xs2 = wsum(xs2);
+    double px = 0.0, py = 0.0, pt = 0.0;
+    for (int m = 0; m < R; m++) {
+        const RayTerms r = ray_terms(lane, N, R, ns, X, pp, SP, m, eta);
+        px += r.Sx; py += r.Sy; pt += r.tq;
+        const double d = X[3 + m], e0 = -((P.lw != 0.0 ? -2.0 * P.lw / (d * d * d) : 0.0) + r.td);
+        if (lane == 0) {
+            if (lgd) lgd[m] = e0;
+            if (lp) { lp[6 + m] = e0; lp[6 + R + m] = -r.tq; }
+        }
+    }
+    if (lane == 0) {
+        double s, c, f0, f1, f2;
+        sincos(X[2], &s, &c);
+        stage_pose_terms(P, pp, X[0], X[1], X[2], U[0], s, c, lam(1, 0), lam(1, 1), lam(1, 2), f0, f1, f2);
+        const double l0 = -(f0 + px), l1 = -(f1 + py), l2 = -(f2 + pt);
+        if (lg) { lg[0] = l0; lg[1] = l1; lg[2] = l2; }
+        if (lp) { lp[0] = l0; lp[1] = l1; lp[2] = l2; lp[3] = 2.0 * P.q[0] * xs0; lp[4] = 2.0 * P.q[1] * xs1; lp[5] = 2.0 * P.q[2] * xs2; }
+    }
+}
+
+// grad_lag = grad f + J' lam_g + lam_x and res = (stat, eq, ineq, bnd, compl, sign) of any (w, lam_g, lam_x): lane k forms the gradient in X_k
+// (k >= 1) and in the control decided at stage k, the residuals of the defect row k + 1 and of the distance rows of stage k; the held control is
+// a wave sum over its stages; X_0 collects every distance row through the lidar points, one wave sum per ray.
+__global__ __launch_bounds__(64) void lidar_kkt_kernel(const LParams P, int B, const double *__restrict__ p_in, const double *__restrict__ w,
+                                                        const double *__restrict__ lam_g, const double *__restrict__ lam_x, double *__restrict__ res_out,
+                                                        double *__restrict__ grad_out)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const int N = P.N, Nc = P.Nc, R = P.R, ns = P.ns, NP1 = N + 1;
+    const double *X = w + (size_t)b * P.nvar, *U = X + (size_t)NP1 * ns, *pp = p_in + (size_t)b * P.np;
+    const double *lg = lam_g + (size_t)b * P.ng, *lgd = lg + 3 * NP1, *lxX = lam_x + (size_t)b * P.nvar, *lxU = lxX + (size_t)NP1 * ns;
+    double *gX = grad_out ? grad_out + (size_t)b * P.nvar : nullptr, *gU = gX ? gX + (size_t)NP1 * ns : nullptr;
+    const double *lbu = P.lb + (size_t)NP1 * ns, *ubu = P.ub + (size_t)NP1 * ns;
+    __shared__ double SP[2 * NMPC_LIDAR_MAX_RAYS];
+    lidar_points(lane, R, X, pp, SP);
+    double stat = 0.0, eq = 0.0, bnd = 0.0, cmp = 0.0, sg = 0.0, hu0 = 0.0, hu1 = 0.0;
+    auto var = [&](double v, double l, double lo, double hi) {      // one variable lo <= v <= hi (either may be infinite) with multiplier l
+        const bool has_lo = lo > -INFINITY, has_hi = hi < INFINITY;
+        const double ln = l > 0.0 ? 0.0 : -l, lq = l < 0.0 ? 0.0 : l;      // the parts that belong to the lower / upper bound; a NaN stays one
+        nan_max(bnd, lo - v); nan_max(bnd, v - hi);
+        if (has_lo) nan_max(cmp, ln * (v - lo));
+        if (has_hi) nan_max(cmp, lq * (hi - v));
+        if (has_lo && !has_hi) nan_max(sg, l);
+        if (has_hi && !has_lo) nan_max(sg, -l);
+    };
+    auto slb = [&](int k, int c) { return k ? P.lb[(size_t)c * NP1 + k] : P.lb0[c]; };
+    auto sub = [&](int k, int c) { return k ? P.ub[(size_t)c * NP1 + k] : P.ub0[c]; };
+    auto eta = [&](int k, int m) { return lgd[R * k + m]; };
+    for (int k = lane; k <= N; k += 64) {
+        const double *v = X + (size_t)k * ns;
+        const double x = v[0], y = v[1], t = v[2];
+        double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+        if (k < N) {
+            const int j = k < Nc - 1 ? k : Nc - 1;
+            const double u0 = U[2 * j], u1 = U[2 * j + 1], l0 = lg[3 * (k + 1)], l1 = lg[3 * (k + 1) + 1], l2 = lg[3 * (k + 1) + 2];
+            double s, c;
+            sincos(t, &s, &c);
+            stage_pose_terms(P, pp, x, y, t, u0, s, c, l0, l1, l2, g0, g1, g2);
+            nan_max(eq, fabs(v[ns] - (x + P.T * u0 * c))); nan_max(eq, fabs(v[ns + 1] - (y + P.T * u0 * s))); nan_max(eq, fabs(v[ns + 2] - (t + P.T * u1)));
+            const double gu0 = 2.0 * P.r[0] * u0 - P.T * (c * l0 + s * l1), gu1 = 2.0 * P.r[1] * u1 - P.T * l2;
+            if (k < Nc - 1) {
+                const double a0 = gu0 + lxU[2 * j], a1 = gu1 + lxU[2 * j + 1];
+                nan_max(stat, fabs(a0)); nan_max(stat, fabs(a1));
+                if (gU) { gU[2 * j] = a0; gU[2 * j + 1] = a1; }
+            } else { hu0 += gu0; hu1 += gu1; }
+        }
+        if (k == 0) continue;      // X_0: after the ray sums below
+        g0 += lxX[(size_t)k * ns] + lg[3 * k]; g1 += lxX[(size_t)k * ns + 1] + lg[3 * k + 1]; g2 += lxX[(size_t)k * ns + 2] + lg[3 * k + 2];
+        var(x, lxX[(size_t)k * ns], slb(k, 0), sub(k, 0)); var(y, lxX[(size_t)k * ns + 1], slb(k, 1), sub(k, 1)); var(t, lxX[(size_t)k * ns + 2], slb(k, 2), sub(k, 2));
+        for (int m = 0; m < R; m++) {
+            const double d = v[3 + m], l = lxX[(size_t)k * ns + 3 + m], e = eta(k, m), ax = x - SP[2 * m], ay = y - SP[2 * m + 1];
+            g0 -= e * sgn(ax); g1 -= e * sgn(ay);
+            double gd = l + e;
+            if (k < N && P.lw != 0.0) gd += -2.0 * P.lw / (d * d * d);
+            nan_max(eq, fabs(d - (fabs(ax) + fabs(ay))));
+            var(d, l, slb(k, 3 + m), sub(k, 3 + m));
+            nan_max(stat, fabs(gd));
+            if (gX) gX[(size_t)k * ns + 3 + m] = gd;
+        }
+        nan_max(stat, fabs(g0)); nan_max(stat, fabs(g1)); nan_max(stat, fabs(g2));
+        if (gX) { gX[(size_t)k * ns] = g0; gX[(size_t)k * ns + 1] = g1; gX[(size_t)k * ns + 2] = g2; }
+    }
+    for (int e = lane; e < 2 * Nc; e += 64) var(U[e], lxU[e], lbu[e], ubu[e]);
+    hu0 = wsum(hu0); hu1 = wsum(hu1);      // the held control: the sum over its stages
+    double px = 0.0, py = 0.0, pt = 0.0;
+    for (int m = 0; m < R; m++) {
+        const RayTerms r = ray_terms(lane, N, R, ns, X, pp, SP, m, eta);
+        px += r.Sx; py += r.Sy; pt += r.tq;
+        if (lane == 0) {
+            const double d = X[3 + m], l = lxX[3 + m], gd = l + lgd[m] + (P.lw != 0.0 ? -2.0 * P.lw / (d * d * d) : 0.0) + r.td;
+            nan_max(eq, fabs(d - pp[6 + m]));
+            var(d, l, slb(0, 3 + m), sub(0, 3 + m));
+            nan_max(stat, fabs(gd));
+            if (gX) gX[3 + m] = gd;
+        }
+    }
+    if (lane == 0) {
+        double s, c, g0, g1, g2;
+        sincos(X[2], &s, &c);
+        stage_pose_terms(P, pp, X[0], X[1], X[2], U[0], s, c, lg[3], lg[4], lg[5], g0, g1, g2);
+        g0 += lxX[0] + lg[0] + px; g1 += lxX[1] + lg[1] + py; g2 += lxX[2] + lg[2] + pt;
+        nan_max(eq, fabs(X[0] - pp[0])); nan_max(eq, fabs(X[1] - pp[1])); nan_max(eq, fabs(X[2] - pp[2]));
+        var(X[0], lxX[0], slb(0, 0), sub(0, 0)); var(X[1], lxX[1], slb(0, 1), sub(0, 1)); var(X[2], lxX[2], slb(0, 2), sub(0, 2));
+        nan_max(stat, fabs(g0)); nan_max(stat, fabs(g1)); nan_max(stat, fabs(g2));
+        if (gX) { gX[0] = g0; gX[1] = g1; gX[2] = g2; }
+        const int j = Nc - 1;
+        const double a0 = hu0 + lxU[2 * j], a1 = hu1 + lxU[2 * j + 1];
+        nan_max(stat, fabs(a0)); nan_max(stat, fabs(a1));
+        if (gU) { gU[2 * j] = a0; gU[2 * j + 1] = a1; }
+    }
+    stat = wave_nan_max(stat); eq = wave_nan_max(eq); bnd = wave_nan_max(bnd); cmp = wave_nan_max(cmp); sg = wave_nan_max(sg);
+    if (lane == 0) {
+        double *r = res_out + (size_t)b * 6;
+        r[0] = stat; r[1] = eq; r[2] = 0.0; r[3] = bnd; r[4] = cmp; r[5] = sg;      // ineq: this NLP's rows are all equalities
+    }
+}
+
 // warm-start shuffle V4:258-270
 __global__ __launch_bounds__(256) void lidar_shift_kernel(const LParams P, int B, const double *__restrict__ w_in, double *__restrict__ w_next)
 {
@@ -1144,6 +1345,31 @@ int32_t nmpc_lidar_solve_batch(nmpc_lidar_handle_t *h, int32_t B, const double *
     // default of 64 KB (a second handle with another horizon would otherwise change the limit under this one)
     if (h->lds_bytes > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) != hipSuccess) return NMPC_E_HIP;
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), h->lds_bytes, (hipStream_t)stream, h->P, B, p, w0, w_out, obj, status, iters, kkt, h->ws);
+    return hipGetLastError() == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+/* the plain call (its argument checks, its launch choice, its kernel), then one launch that reads the multipliers out of the workspace */
+int32_t nmpc_lidar_solve_batch_duals(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w0, double *w_out, double *obj, int32_t *status,
+                                     int32_t *iters, double *kkt, const nmpc_duals_t *duals, void *stream)
+{
+    const int32_t rc = nmpc_lidar_solve_batch(h, B, p, w0, w_out, obj, status, iters, kkt, stream);
+    if (rc != NMPC_OK || B == 0 || !duals || (!duals->lam_g && !duals->lam_x && !duals->lam_p)) return rc;
+    LidarDeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    hipLaunchKernelGGL(nmpc_lidar::lidar_duals_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, h->P, B, p, w_out, h->ws, duals->lam_g, duals->lam_x,
+                       duals->lam_p);
+    return hipGetLastError() == hipSuccess ? NMPC_OK : NMPC_E_HIP;
+}
+
+int32_t nmpc_lidar_kkt_batch(nmpc_lidar_handle_t *h, int32_t B, const double *p, const double *w, const double *lam_g, const double *lam_x, double *res,
+                             double *grad_lag, void *stream)
+{
+    if (!h || B < 0) return NMPC_E_ARG;
+    if (B == 0) return NMPC_OK;
+    if (!p || !w || !lam_g || !lam_x || !res) return NMPC_E_ARG;
+    LidarDeviceScope dev(h->device);
+    if (!dev.ok) return NMPC_E_HIP;
+    hipLaunchKernelGGL(nmpc_lidar::lidar_kkt_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, h->P, B, p, w, lam_g, lam_x, res, grad_lag);
     return hipGetLastError() == hipSuccess ? NMPC_OK : NMPC_E_HIP;
 }
 

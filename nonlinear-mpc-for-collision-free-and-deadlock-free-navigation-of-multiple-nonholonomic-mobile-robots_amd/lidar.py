@@ -132,7 +132,10 @@ class LidarSolver:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
-    def solve_batch(self, p, w0, want_fg: bool = False):
+    def solve_batch(self, p, w0, want_fg: bool = False, want_duals: bool = False):
+        """sol = solver(x0=, p=, ...) (V4:245) for B robots: x [B, n_var], f, status, iters, kkt [B]; want_fg: f and g [B, n_g] of the returned
+        point (nmpc_lidar_eval_batch); want_duals: also the multipliers of the returned point, lam_g [B, n_g], lam_x [B, n_var], lam_p [B, n_p],
+        in CasADi's layout and sign (nmpc_lidar_solve_batch_duals, include/nmpc_lidar.h); the other outputs do not depend on it."""
         torch = self.torch
         p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
         w0 = self._dev(w0, (B, self.n_var))
@@ -141,10 +144,19 @@ class LidarSolver:
         w = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device)
         obj = torch.empty(B, dtype=torch.float64, device=self.device); kkt = torch.empty(B, dtype=torch.float64, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device); iters = torch.empty(B, dtype=torch.int32, device=self.device)
+        lam = {}
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.nmpc_lidar_solve_batch(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(),
-                                                       iters.data_ptr(), kkt.data_ptr(), self._stream()), "nmpc_lidar_solve_batch")
-        out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt)
+            if want_duals:
+                lam = dict(lam_g=torch.empty((B, self.n_g), dtype=torch.float64, device=self.device),
+                           lam_x=torch.empty((B, self.n_var), dtype=torch.float64, device=self.device),
+                           lam_p=torch.empty((B, self.n_p), dtype=torch.float64, device=self.device))
+                cd = _lib.CDuals(lam["lam_g"].data_ptr(), lam["lam_x"].data_ptr(), lam["lam_p"].data_ptr())
+                _lib.check(self.lib.nmpc_lidar_solve_batch_duals(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(),
+                                                                 iters.data_ptr(), kkt.data_ptr(), C.byref(cd), self._stream()), "nmpc_lidar_solve_batch_duals")
+            else:
+                _lib.check(self.lib.nmpc_lidar_solve_batch(self._h, B, p.data_ptr(), w0.data_ptr(), w.data_ptr(), obj.data_ptr(), status.data_ptr(),
+                                                           iters.data_ptr(), kkt.data_ptr(), self._stream()), "nmpc_lidar_solve_batch")
+        out = dict(x=w, f=obj, status=status, iters=iters, kkt=kkt, **lam)
         if want_fg:
             out["f"], out["g"] = self.eval_batch(p, w)
         return out
@@ -157,6 +169,20 @@ class LidarSolver:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.nmpc_lidar_eval_batch(self._h, B, p.data_ptr(), w.data_ptr(), f.data_ptr(), g.data_ptr(), self._stream()), "nmpc_lidar_eval_batch")
         return f, g
+
+    def kkt_batch(self, p, w, lam_g, lam_x, want_grad: bool = False):
+        """KKT residuals of (w, lam_g, lam_x) for B instances on the device (nmpc_lidar_kkt_batch): res [B, 6] = (stat, eq, ineq, bnd, compl, sign)
+        as include/nmpc_lidar.h defines them, and with want_grad also grad_lag [B, n_var] = grad f + J' lam_g + lam_x.  The multipliers may be a
+        solve's (want_duals=True) or any others.  Uses no workspace: B is not bounded by max_batch."""
+        torch = self.torch
+        p = self._dev(p, (-1, self.n_p)); B = p.shape[0]
+        w = self._dev(w, (B, self.n_var)); lam_g = self._dev(lam_g, (B, self.n_g)); lam_x = self._dev(lam_x, (B, self.n_var))
+        res = torch.empty((B, 6), dtype=torch.float64, device=self.device)
+        grad = torch.empty((B, self.n_var), dtype=torch.float64, device=self.device) if want_grad else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nmpc_lidar_kkt_batch(self._h, B, p.data_ptr(), w.data_ptr(), lam_g.data_ptr(), lam_x.data_ptr(), res.data_ptr(),
+                                                     grad.data_ptr() if want_grad else None, self._stream()), "nmpc_lidar_kkt_batch")
+        return (res, grad) if want_grad else res
 
     def shift_batch(self, w):
         """V4:258-270 on device: U rows drop first / repeat last; X rows [X_1..X_N; X_{N-1}]."""
@@ -207,11 +233,13 @@ class LidarSolver:
                 raise ValueError(f"{name} has {g.size} entries, expected {want.size}")
             if not np.array_equal(g, want):
                 raise ValueError(f"{name} differs from the bounds this solver was built with; build a new solver instead")
-        r = self.solve_batch(p[None], w0[None], want_fg=True)
+        r = self.solve_batch(p[None], w0[None], want_fg=True, want_duals=True)
         self.torch.cuda.synchronize(self.device)
         st = int(r["status"][0])
         self._stats = dict(return_status=_lib.STATUS_NAMES.get(st, str(st)), success=(st == 0), iter_count=int(r["iters"][0]), kkt_error=float(r["kkt"][0]), status_code=st)
-        return {"x": r["x"][0].cpu().numpy().reshape(-1, 1), "f": float(r["f"][0]), "g": r["g"][0].cpu().numpy().reshape(-1, 1)}
+        sol = {"x": r["x"][0].cpu().numpy().reshape(-1, 1), "f": float(r["f"][0]), "g": r["g"][0].cpu().numpy().reshape(-1, 1)}
+        sol.update({k: r[k][0].cpu().numpy().reshape(-1, 1) for k in ("lam_g", "lam_x", "lam_p")})      # sol['lam_g'], sol['lam_x'], sol['lam_p'] of CasADi
+        return sol
 
     def stats(self) -> Dict:
         return dict(self._stats)
